@@ -10,6 +10,19 @@ produced in device memory.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
                     [--utts U] [--dist-backend nccl|gloo] [--share-device]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it builds the inputs,
+runs W warmup steps, times K steps, checks the step's flag, writes its
+outputs if `--dump-outputs DIR` is given (a fixed seeded sample of the SIF
+and MMB2 rows the last timed step returned, DIR/sif.npy, DIR/mmb2.npy and
+their row numbers DIR/rows.npy; the inputs are seeded, so two runs with the
+same arguments write the same rows) and prints the result line: `metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (milliseconds per
+timed step), the run's configuration.  Everything below that is measured
+beside the headline -- per-phase times from K more steps under HIP events,
+the rooflines, `per_rank_steps`, `configs_measured`, the CPU baselines, the
+HBM ceilings -- runs only with `--full` (minutes, not seconds).
 
 Scaling (configs[3]: "1M utterances ... utterance-sharded across 8 x MI355X
 ... 1/2/4/8-GPU scaling curve"): STRONG by default -- one 1M-utterance split,
@@ -31,9 +44,9 @@ same multi-rank branch with every rank on GPU 0 and the collectives on gloo
 `--dump-rows DIR` each rank saves its PC and a sample of its rows).  Rank 0
 prints ONE JSON line.
 
-At N = 1 the line also carries `per_rank_steps` -- the step at the per-rank
-sizes of the 2/4/8-GPU strong-scaling runs (500k / 250k / 125k rows of the
-same split) -- and `configs_measured`, the other BASELINE configs measured in
+With `--full`, at N = 1 the line also carries `per_rank_steps` -- the step at
+the per-rank sizes of the 2/4/8-GPU strong-scaling runs (500k / 250k / 125k
+rows of the same split) -- and `configs_measured`, the other BASELINE configs measured in
 the same run: configs[0] (MMB1 text SIF at MOSI shape, GPU and the reference
 CPU path), configs[1] (MMB2 at MOSI shape), the ragged configs[3] variant
 (Poisson(40) lengths in [1, 64]), configs[2] (POM transcript
@@ -1029,6 +1042,35 @@ def dump_rows(path, rank, row0, step):
              mmb2=step.mmb2[idx].cpu().numpy(), flag=int(step.flag.item()))
 
 
+DUMP_SAMPLE_ROWS = 16384  # x 300 f32 x 2 outputs = 39 MB
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(path, rank, world, row0, step, sif, mmb2):
+    """--dump-outputs: what the last timed FusedStep.run returned -- the SIF
+    rows and the MMB2 rows, both [n, 300] f32 -- as <path>/sif.npy and
+    <path>/mmb2.npy, and the rows' indices in the split as rows.npy (f64).  A
+    split larger than DUMP_SAMPLE_ROWS is sampled: the same seeded rows every
+    run, so two builds are compared output for output.  With more than one
+    rank every rank saves its own rows as <name>_rank<r>.npy."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    n = step.n
+    if n > DUMP_SAMPLE_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_SAMPLE_ROWS,
+                                                                      replace=False))
+    else:
+        rows = np.arange(n)
+    idx = torch.as_tensor(rows, device=sif.device)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in (("sif", sif[idx].float().cpu().numpy()),
+                    ("mmb2", mmb2[idx].float().cpu().numpy()),
+                    ("rows", (row0 + rows).astype(np.float64))):
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1056,6 +1098,13 @@ def main():
                     help="every rank on GPU 0 (tests of the N > 1 branch on a one-GPU box)")
     ap.add_argument("--dump-rows", default=None,
                     help="directory: each rank saves its PC and a sample of its rows")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, save what the last timed step returned (a fixed "
+                         "seeded sample of the SIF and MMB2 rows) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else: per-phase times "
+                         "and rooflines, per_rank_steps, configs_measured, the CPU baselines and "
+                         "the HBM ceilings (minutes); without it only the headline is measured")
     ap.add_argument("--chunks", type=int, default=None,
                     help="row chunks per step (stream of chunk c+1 overlaps projection of c); "
                          "default 1")
@@ -1147,7 +1196,7 @@ def main():
         inp.pop("lengths", None)
     ids = inp["ids"]
     text_rows = None
-    if kind in ("pom", "ragged"):
+    if args.full and kind in ("pom", "ragged"):  # the rooflines' text-row count
         text_rows = (ids != 0).sum().item() / U + (ids == 0).any(1).float().mean().item()
     torch.manual_seed(0)
     gen = models.AudioVisualGeneratorMultimodal(D, A, Vd, norm=None).to(dev)
@@ -1164,17 +1213,17 @@ def main():
         step.run()
     torch.cuda.synchronize()
 
-    # timed region: K steps, barrier + sync on both sides.  Then K more steps
-    # with HIP events recorded on the stream each phase is launched on
-    # (FusedStep.run trace) for phase_ms and the kernels' launch durations --
-    # outside the timed region (r05: ~12 event markers per step had been
-    # inside it)
+    # timed region: K steps, barrier + sync on both sides.  With --full, K
+    # more steps follow with HIP events recorded on the stream each phase is
+    # launched on (FusedStep.run trace) for phase_ms and the kernels' launch
+    # durations -- outside the timed region (r05: ~12 event markers per step
+    # had been inside it)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step.run()
+        sif_out, mmb2_out = step.run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -1184,28 +1233,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     step.check()  # ids in range, no all-zero-weight utterance, finite PC (every rank)
-    traces = [dict() for _ in range(args.steps)]
-    for k in range(args.steps):
-        step.run(trace=traces[k])
-    torch.cuda.synchronize()
-    step.check()
-    if args.dump_rows:
-        dump_rows(args.dump_rows, rank, row0, step)
-
-    phase_ms = phase_times(traces, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, row0, step, sif_out, mmb2_out)
     ms_per_step = elapsed * 1e3 / args.steps
     value = U_total * args.steps / elapsed
+    if args.full:
+        traces = [dict() for _ in range(args.steps)]
+        for k in range(args.steps):
+            step.run(trace=traces[k])
+        torch.cuda.synchronize()
+        step.check()
+        phase_ms = phase_times(traces, args.steps)
+    if args.dump_rows:
+        dump_rows(args.dump_rows, rank, row0, step)
     if rank != 0:
         dist.destroy_process_group()
         return 0
 
-    utts_per_launch = U // len(step.bounds) if len(step.bounds) > 1 else U
-    kb, kname = dominant_kernel(step, T, D, text_rows=text_rows)
-    roof = stream_roofline(phase_ms, traces, args.steps, kb, utts_per_launch, kname, kind, T)
-    if kind == "mosi":
-        table_resident_roofline(roof, kb, utts_per_launch, D, T, narrow_fused=step.narrow_fused)
-    pb = path_bytes(T, D, A, Vd, text_rows=text_rows)
-    mfma = mfma_rooflines(step, phase_ms, U, D)
     wl = {"synthetic": "configs[3]: synthetic utterances x 40 tokens/frames x 3 modalities x "
                        "300d, V = 400k, Zipf(1.1) ids, SIF(+PC removal) + closed-form MMB2",
           "pom": "configs[2]: POM-shaped (V=7763, w0=1.0, transcripts padded to 1357, ~370 "
@@ -1234,6 +1278,27 @@ def main():
                                   f"{scaling} scaling) + one all-reduce of the 300x300 fp64 Gram "
                                   f"({'RCCL' if args.dist_backend == 'nccl' else 'gloo'})"
                                   + (", all ranks on GPU 0" if args.share_device else "")},
+        "full": args.full,
+    }
+    if args.dump_outputs:
+        out["dump_outputs"] = args.dump_outputs
+    if args.dump_rows:
+        out["dump_rows"] = args.dump_rows
+    if not args.full:  # the headline only
+        out["chunks"] = len(step.bounds)
+        print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
+
+    utts_per_launch = U // len(step.bounds) if len(step.bounds) > 1 else U
+    kb, kname = dominant_kernel(step, T, D, text_rows=text_rows)
+    roof = stream_roofline(phase_ms, traces, args.steps, kb, utts_per_launch, kname, kind, T)
+    if kind == "mosi":
+        table_resident_roofline(roof, kb, utts_per_launch, D, T, narrow_fused=step.narrow_fused)
+    pb = path_bytes(T, D, A, Vd, text_rows=text_rows)
+    mfma = mfma_rooflines(step, phase_ms, U, D)
+    out.update({
         "roofline": roof,
         "path_roofline": {"bytes_per_utt": round(pb, 1),
                           "achieved": round(pb * U / (ms_per_step / 1e3) / 1e9, 1),
@@ -1242,7 +1307,7 @@ def main():
         "phase_ms": {k: round(v, 4) for k, v in phase_ms.items()},
         "mfma_rooflines": mfma,
         "chunks": len(step.bounds),
-    }
+    })
     if "pc_remove" in phase_ms:  # separate removal pass: x read, SIF row written
         rb = 2 * 4 * D
         ach = rb * U / (phase_ms["pc_remove"] / 1e3) / 1e9
@@ -1252,8 +1317,6 @@ def main():
                                      "ms": round(phase_ms["pc_remove"], 4)}
     if world > 1:
         out["phase_ms"].setdefault("allreduce", None)
-    if args.dump_rows:
-        out["dump_rows"] = args.dump_rows
     cpu = None
     extras = world == 1 and not args.only_main and kind == "synthetic"
     if extras:

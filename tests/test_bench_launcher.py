@@ -40,6 +40,45 @@ def test_single_rank_launch_check_runs_in_process():
     assert "launching" not in r.stderr
 
 
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, the same seeded rows on
+    every call, at most 64 MB at the bench shape (300-d rows), every row of a
+    split no larger than the sample."""
+    import types
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert 2 * bench.DUMP_SAMPLE_ROWS * 300 * 4 + bench.DUMP_SAMPLE_ROWS * 8 <= 64 << 20
+    n = bench.DUMP_SAMPLE_ROWS + 1000
+    sif = torch.arange(n, dtype=torch.float32)[:, None].repeat(1, 3)
+    mmb2 = -sif
+    step = types.SimpleNamespace(n=n)
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.dump_outputs(a, 0, 1, 0, step, sif, mmb2)
+    bench.dump_outputs(b, 0, 1, 0, step, sif, mmb2)
+    assert sorted(os.listdir(a)) == ["mmb2.npy", "rows.npy", "sif.npy"]
+    za = {f: np.load(os.path.join(a, f)) for f in os.listdir(a)}
+    for f, arr in za.items():
+        assert arr.dtype in (np.float32, np.float64), f
+        assert np.array_equal(arr, np.load(os.path.join(b, f))), f
+    rows = za["rows.npy"]
+    assert rows.shape == (bench.DUMP_SAMPLE_ROWS,) and np.all(np.diff(rows) > 0)
+    assert rows[0] >= 0 and rows[-1] < n
+    assert np.array_equal(za["sif.npy"][:, 0], rows)
+    assert np.array_equal(za["mmb2.npy"], -za["sif.npy"])
+    # a small split whole; a rank's rows are numbered in the split and named by rank
+    small = types.SimpleNamespace(n=10)
+    c = str(tmp_path / "c")
+    bench.dump_outputs(c, 1, 2, 40, small, sif[:10], mmb2[:10])
+    assert sorted(os.listdir(c)) == ["mmb2_rank1.npy", "rows_rank1.npy", "sif_rank1.npy"]
+    assert np.array_equal(np.load(os.path.join(c, "rows_rank1.npy")), np.arange(40.0, 50.0))
+    assert np.array_equal(np.load(os.path.join(c, "sif_rank1.npy")), sif[:10].numpy())
+
+
 def test_algorithmic_bytes_match_survey():
     sys.path.insert(0, ROOT)
     import bench

@@ -10,7 +10,7 @@ cd /tmp
 for W in "$@"; do
   for C in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc $C -d "$OUT/pmc_${W}_${C}" -o run --output-format csv \
-      -- python3 "$REPO/bench.py" --workload $W --steps 2 --warmup 1 --only-main --no-cpu-baseline \
+      -- python3 "$REPO/bench.py" --full --workload $W --steps 2 --warmup 1 --only-main --no-cpu-baseline \
       > "$OUT/pmc_${W}_${C}.json" 2> "$OUT/pmc_${W}_${C}.err"
     rc=$?; echo "pmc $W $C rc=$rc"; [ $rc -eq 0 ] || exit $rc
   done

@@ -15,14 +15,14 @@ export TMPDIR=/tmp
 REPO=$PWD
 ok() { local rc=$1; [ "$rc" -eq 0 ] || { echo "step failed rc=$rc"; exit "$rc"; }; }
 
-timeout -k 10 900 python3 "$REPO/bench.py" --steps "$STEPS" --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"; ok $?
+timeout -k 10 900 python3 "$REPO/bench.py" --full --steps "$STEPS" --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"; ok $?
 echo "bench: $(cat "$OUT/bench.json")"
 cd /tmp
 timeout -k 10 900 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
-  -- python3 "$REPO/bench.py" --steps "$STEPS" --warmup 3 --no-cpu-baseline > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; ok $?
+  -- python3 "$REPO/bench.py" --full --steps "$STEPS" --warmup 3 --no-cpu-baseline > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; ok $?
 timeout -k 10 900 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o run --output-format csv \
-  -- python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"; ok $?
+  -- python3 "$REPO/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"; ok $?
 timeout -k 10 900 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_write" -o run --output-format csv \
-  -- python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"; ok $?
+  -- python3 "$REPO/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"; ok $?
 echo "profiles done"
 find "$OUT" -name "*.csv" | head -20

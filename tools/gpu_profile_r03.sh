@@ -25,19 +25,19 @@ if [ "$PART" = a ]; then
     timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; ok $?
     tail -1 "$OUT/smoke.log"
   fi
-  timeout -k 10 600 python3 "$REPO/bench.py" --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; ok $?
+  timeout -k 10 600 python3 "$REPO/bench.py" --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; ok $?
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('bench', d['value'], d['ms_per_step'], d['phase_ms'])" "$OUT/bench.json"
   cd /tmp
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
-    -- python3 "$REPO/bench.py" --steps 10 --warmup 3 --only-main --no-cpu-baseline > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; ok $?
+    -- python3 "$REPO/bench.py" --full --steps 10 --warmup 3 --only-main --no-cpu-baseline > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; ok $?
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace125k" -o run --output-format csv \
-    -- python3 "$REPO/bench.py" --utts 125000 --steps 20 --warmup 3 --only-main --no-cpu-baseline > "$OUT/trace125k_bench.json" 2> "$OUT/trace125k.err"; ok $?
+    -- python3 "$REPO/bench.py" --full --utts 125000 --steps 20 --warmup 3 --only-main --no-cpu-baseline > "$OUT/trace125k_bench.json" 2> "$OUT/trace125k.err"; ok $?
 else
   cd /tmp
   for W in synthetic ragged pom mosi; do
     for C in FETCH_SIZE WRITE_SIZE; do
       timeout -k 10 600 rocprofv3 --kernel-trace --pmc $C -d "$OUT/pmc_${W}_${C}" -o run --output-format csv \
-        -- python3 "$REPO/bench.py" --workload $W --steps 2 --warmup 1 --only-main --no-cpu-baseline > "$OUT/pmc_${W}_${C}.json" 2> "$OUT/pmc_${W}_${C}.err"; ok $?
+        -- python3 "$REPO/bench.py" --full --workload $W --steps 2 --warmup 1 --only-main --no-cpu-baseline > "$OUT/pmc_${W}_${C}.json" 2> "$OUT/pmc_${W}_${C}.err"; ok $?
     done
   done
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/latent" -o run --output-format csv \

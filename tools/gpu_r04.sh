@@ -24,10 +24,10 @@ for step in "$@"; do
       tail -1 "$OUT/smoke.log"
       ;;
     bench)
-      timeout -k 10 600 python3 -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+      timeout -k 10 600 python3 -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
       ;;
     main)
-      timeout -k 10 300 python3 -u bench.py --only-main --no-cpu-baseline --steps 10 --warmup 3 \
+      timeout -k 10 300 python3 -u bench.py --full --only-main --no-cpu-baseline --steps 10 --warmup 3 \
         > "$OUT/main.json" 2> "$OUT/main.err" || exit $?
       ;;
     *)

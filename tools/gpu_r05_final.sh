@@ -14,19 +14,19 @@ OUT=$PWD/gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp; REPO=$PWD
 ok() { local rc=$1; [ "$rc" -eq 0 ] || { echo "step failed rc=$rc"; exit "$rc"; }; }
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
-  -- python3 "$REPO/bench.py" --steps 10 --warmup 3 --only-main --no-cpu-baseline > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; ok $?
+  -- python3 "$REPO/bench.py" --full --steps 10 --warmup 3 --only-main --no-cpu-baseline > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; ok $?
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace125k" -o run --output-format csv \
-  -- python3 "$REPO/bench.py" --utts 125000 --steps 20 --warmup 10 --only-main --no-cpu-baseline > "$OUT/trace125k_bench.json" 2> "$OUT/trace125k.err"; ok $?
+  -- python3 "$REPO/bench.py" --full --utts 125000 --steps 20 --warmup 10 --only-main --no-cpu-baseline > "$OUT/trace125k_bench.json" 2> "$OUT/trace125k.err"; ok $?
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/tracemosi" -o run --output-format csv \
-  -- python3 "$REPO/bench.py" --workload mosi --steps 10 --warmup 10 --only-main --no-cpu-baseline > "$OUT/tracemosi_bench.json" 2> "$OUT/tracemosi.err"; ok $?
+  -- python3 "$REPO/bench.py" --full --workload mosi --steps 10 --warmup 10 --only-main --no-cpu-baseline > "$OUT/tracemosi_bench.json" 2> "$OUT/tracemosi.err"; ok $?
 for W in synthetic mosi; do
   for C in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc $C -d "$OUT/pmc_${W}_${C}" -o run --output-format csv \
-      -- python3 "$REPO/bench.py" --workload $W --steps 2 --warmup 1 --only-main --no-cpu-baseline \
+      -- python3 "$REPO/bench.py" --full --workload $W --steps 2 --warmup 1 --only-main --no-cpu-baseline \
       > "$OUT/pmc_${W}_${C}.json" 2> "$OUT/pmc_${W}_${C}.err"; ok $?
   done
 done
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum -d "$OUT/pmc_mosi_TCC" -o run --output-format csv \
-  -- python3 "$REPO/bench.py" --workload mosi --steps 2 --warmup 1 --only-main --no-cpu-baseline \
+  -- python3 "$REPO/bench.py" --full --workload mosi --steps 2 --warmup 1 --only-main --no-cpu-baseline \
   > "$OUT/pmc_mosi_TCC.json" 2> "$OUT/pmc_mosi_TCC.err"; ok $?
 echo "final profile $TAG done"

@@ -13,18 +13,18 @@ ok() { local rc=$1; [ "$rc" -eq 0 ] || { echo "step failed rc=$rc"; exit "$rc"; 
 cd /tmp
 if [ "$PART" = trace ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
-    -- python3 "$REPO/bench.py" --steps 10 --warmup 3 --only-main --no-cpu-baseline > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; ok $?
+    -- python3 "$REPO/bench.py" --full --steps 10 --warmup 3 --only-main --no-cpu-baseline > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; ok $?
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace125k" -o run --output-format csv \
-    -- python3 "$REPO/bench.py" --utts 125000 --steps 20 --warmup 10 --only-main --no-cpu-baseline > "$OUT/trace125k_bench.json" 2> "$OUT/trace125k.err"; ok $?
+    -- python3 "$REPO/bench.py" --full --utts 125000 --steps 20 --warmup 10 --only-main --no-cpu-baseline > "$OUT/trace125k_bench.json" 2> "$OUT/trace125k.err"; ok $?
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/tracemosi" -o run --output-format csv \
-    -- python3 "$REPO/bench.py" --workload mosi --steps 10 --warmup 10 --only-main --no-cpu-baseline > "$OUT/tracemosi_bench.json" 2> "$OUT/tracemosi.err"; ok $?
+    -- python3 "$REPO/bench.py" --full --workload mosi --steps 10 --warmup 10 --only-main --no-cpu-baseline > "$OUT/tracemosi_bench.json" 2> "$OUT/tracemosi.err"; ok $?
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/tracepom" -o run --output-format csv \
-    -- python3 "$REPO/bench.py" --workload pom --steps 10 --warmup 5 --only-main --no-cpu-baseline > "$OUT/tracepom_bench.json" 2> "$OUT/tracepom.err"; ok $?
+    -- python3 "$REPO/bench.py" --full --workload pom --steps 10 --warmup 5 --only-main --no-cpu-baseline > "$OUT/tracepom_bench.json" 2> "$OUT/tracepom.err"; ok $?
 else
   for W in synthetic mosi ragged pom; do
     for C in FETCH_SIZE WRITE_SIZE; do
       timeout -k 10 300 rocprofv3 --kernel-trace --pmc $C -d "$OUT/pmc_${W}_${C}" -o run --output-format csv \
-        -- python3 "$REPO/bench.py" --workload $W --steps 2 --warmup 1 --only-main --no-cpu-baseline \
+        -- python3 "$REPO/bench.py" --full --workload $W --steps 2 --warmup 1 --only-main --no-cpu-baseline \
         > "$OUT/pmc_${W}_${C}.json" 2> "$OUT/pmc_${W}_${C}.err"; ok $?
     done
   done

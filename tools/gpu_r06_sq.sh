@@ -14,6 +14,6 @@ cat "$OUT/pc_time.json"
 timeout -k 10 300 python3 bench.py --only-leg dataset_splits > "$OUT/splits.json" 2> "$OUT/splits.err"; ok $?
 python3 -c "import json,sys; d=json.load(open(sys.argv[1]))['dataset_splits']; [print(k, d[k]['all_splits_one_graph_concurrent_ms'], {s: (v['graph_ms'], v['phase_ms'].get('pc_solve')) for s, v in d[k]['splits'].items()}) for k in ('mosi','pom')]" "$OUT/splits.json"
 for i in 1 2; do
-  timeout -k 10 300 python3 bench.py --utts-per-gpu 125000 --only-main --no-cpu-baseline --steps 50 --warmup 10 > "$OUT/step125k_$i.json" 2> "$OUT/step125k_$i.err"; ok $?
+  timeout -k 10 300 python3 bench.py --full --utts-per-gpu 125000 --only-main --no-cpu-baseline --steps 50 --warmup 10 > "$OUT/step125k_$i.json" 2> "$OUT/step125k_$i.err"; ok $?
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('125k', d['ms_per_step'], d.get('phase_ms'))" "$OUT/step125k_$i.json"
 done

@@ -12,7 +12,7 @@ for v in "$@" "$@"; do
   echo "variant=$v $r"
 done
 for v in "$@"; do
-  MMB_PROJ_VARIANT=$v timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_v$v.json" 2> "$OUT/bench_v$v.err"
+  MMB_PROJ_VARIANT=$v timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_v$v.json" 2> "$OUT/bench_v$v.err"
   rc=$?; [ "$rc" -eq 0 ] || { tail -3 "$OUT/bench_v$v.err"; exit "$rc"; }
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('variant', sys.argv[2], d['value'], d['ms_per_step'], d['phase_ms'])" "$OUT/bench_v$v.json" "$v"
 done

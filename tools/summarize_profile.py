@@ -71,7 +71,7 @@ def main(src, tag):
                   f"stream kernel avg launch: HIP events {ev:.4f} ms, rocprofv3 "
                   f"{rp[0] if rp else float('nan'):.4f} ms; traced-run value {tb['value']:.1f} utt/s, "
                   f"{tb['ms_per_step']:.4f} ms/step", ""]
-    lines += ["## kernel stats (`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 "
+    lines += ["## kernel stats (`rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 "
               "--warmup 3 --no-cpu-baseline`)", "",
               "| kernel | calls | avg ms | total % |", "|---|---|---|---|"]
     for r in stats:

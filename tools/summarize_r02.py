@@ -44,7 +44,7 @@ def main(src, tag):
               f"stream kernel avg launch: HIP events {tb['roofline']['avg_launch_ms']:.4f} ms, "
               f"rocprofv3 {rp[0] if rp else float('nan'):.4f} ms; traced-run value "
               f"{tb['value']:.1f} utt/s, {tb['ms_per_step']:.4f} ms/step", "",
-              "## kernel stats (`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 "
+              "## kernel stats (`rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 "
               "--warmup 3 --only-main --no-cpu-baseline`)", "",
               "| kernel | calls | avg ms | total % |", "|---|---|---|---|"]
     for r in stats:

@@ -48,7 +48,7 @@ def main(src, tag):
               f"stream kernel avg launch: HIP events {tb['roofline']['avg_launch_ms']:.4f} ms, "
               f"rocprofv3 {rp[0] if rp else float('nan'):.4f} ms; traced-run value "
               f"{tb['value']:.1f} utt/s, {tb['ms_per_step']:.4f} ms/step", "",
-              "## kernel stats (`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 "
+              "## kernel stats (`rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 "
               "--warmup 3 --only-main --no-cpu-baseline`)", "",
               "| kernel | calls | avg ms | total % |", "|---|---|---|---|"]
     for r in stats:
@@ -63,7 +63,7 @@ def main(src, tag):
                         r["Percentage"]])
     stats125 = list(csv.DictReader(open(os.path.join(src, "trace125k", "run_kernel_stats.csv"))))
     t125 = json.load(open(os.path.join(src, "trace125k_bench.json")))
-    lines += ["## per-rank size of the 8-GPU strong-scaling curve (`bench.py --utts 125000 --steps 20 "
+    lines += ["## per-rank size of the 8-GPU strong-scaling curve (`bench.py --full --utts 125000 --steps 20 "
               "--warmup 3 --only-main --no-cpu-baseline` under rocprofv3)", "",
               f"step {t125['ms_per_step']:.4f} ms; phases (HIP events) {json.dumps(t125['phase_ms'])}", "",
               "| kernel | calls | avg ms | total % |", "|---|---|---|---|"]
