@@ -1941,13 +1941,10 @@ __device__ __forceinline__ void p16_eq_chol(const double* W, double* L, double* 
 constexpr int kSqNT = 256;
 // G2 tiles per squaring workgroup of the solve's launch (two at a time): 2
 // puts 95 workgroups beside the solve's 19 at d = 300, 4 puts 48 (fewer CUs
-// held with the solve's LDS allocation).  Alternated A/B (r06,
-// tools/ab_libs/build_sq.sh, profiles/r06/sq2/): the solve alone 75.1 vs
-// 76.7 us, MOSI's three-split graph 0.215 vs 0.216 ms, POM's 0.343 vs 0.344
-#ifndef MMB_SQ_PER_WG
-#define MMB_SQ_PER_WG 2
-#endif
-constexpr int kSqPerWg = MMB_SQ_PER_WG;
+// held with the solve's LDS allocation).  Measured (r06, profiles/r06/sq2/):
+// the solve alone 75.1 vs 76.7 us, MOSI's three-split graph 0.215 vs
+// 0.216 ms, POM's 0.343 vs 0.344
+constexpr int kSqPerWg = 2;
 static_assert(kSqPerWg % 2 == 0, "two tiles per pass");
 __device__ __forceinline__ void square_tile_ab(int blk, int T, int& a, int& b) {
   int rem = blk;

@@ -451,24 +451,13 @@ struct SplitPlan {
   int Pt, Lt, Pf, Lf;  // text / frame parts per utterance and their lengths
   int Wt, Wf;          // partial row strides (floats, multiples of 4)
 };
-// A/B build constants of the split kernel (tools/ab_libs/build_split.sh):
-// text ranges per frame range of the automatic plan (MMB_SPLIT_TEXT_X; an
-// explicit part count keeps them equal), text / frame rows unrolled per
-// thread group (MMB_SPLIT_TU / MMB_SPLIT_FU; the sums' order is the same).
-// Alternated twice on POM's real splits (r06, profiles/r06/splitab*,
-// valid / test stream ms): TU 8 FU 16 0.0556-0.0567 / 0.126-0.128; FU 8
-// 0.0545-0.0551 / 0.123-0.125 (kept); FU 4 0.067 / 0.146; FU 32 0.065 /
-// 0.141; TU 16 0.072 / 0.151; TU 4 FU 8 0.067 / 0.116; two text ranges per
-// frame range 0.058 / 0.131 -- the text workgroups are not the long pole
-#ifndef MMB_SPLIT_TEXT_X
-#define MMB_SPLIT_TEXT_X 1
-#endif
-#ifndef MMB_SPLIT_TU
-#define MMB_SPLIT_TU 8
-#endif
-#ifndef MMB_SPLIT_FU
-#define MMB_SPLIT_FU 8
-#endif
+// Text ranges per frame range of the automatic plan (an explicit part count
+// keeps them equal) and text / frame rows unrolled per thread group (the
+// sums' order does not depend on them).  Settled on POM's real splits
+// ("Settled kernel constants").
+constexpr int kSplitTextX = 1;
+constexpr int kSplitTU = 8;
+constexpr int kSplitFU = 8;
 inline SplitPlan split_plan_of(int t, int d, int a, int vd, int Pf, int text_x = 1) {
   SplitPlan q;
   q.Lf = (t + Pf - 1) / Pf;
@@ -2823,13 +2812,13 @@ static size_t split_ws_floats(int64_t n, const SplitPlan& q) {
 extern "C" size_t mmb_mm2_stream_split_ws_bytes(int64_t n, int t, int d, int a_, int vd, int parts) {
   if (n <= 0 || t <= 0 || d <= 0 || a_ <= 0 || vd <= 0) return 0;
   const int P = parts > 0 ? std::min(parts, t) : mmb_mm2_stream_split_parts(n, t);
-  return split_ws_floats(n, split_plan_of(t, d, a_, vd, P, parts > 0 ? 1 : MMB_SPLIT_TEXT_X)) * sizeof(float);
+  return split_ws_floats(n, split_plan_of(t, d, a_, vd, P, parts > 0 ? 1 : kSplitTextX)) * sizeof(float);
 }
 
 template <int VT, int VA, int VV>
 static int launch_split(const StreamArgs& a, const SplitPlan& q, float* part, hipStream_t stream) {
   const int64_t grid = a.N * (q.Pt + 2 * q.Pf);
-  utt_split_part_kernel<VT, VA, VV, MMB_SPLIT_FU, MMB_SPLIT_TU><<<static_cast<unsigned>(grid), kNT, 0, stream>>>(a, q, part);
+  utt_split_part_kernel<VT, VA, VV, kSplitFU, kSplitTU><<<static_cast<unsigned>(grid), kNT, 0, stream>>>(a, q, part);
   MMB_LAUNCH_CHECK();
   const size_t lds = a.s_half ? static_cast<size_t>(2 * (a.D + a.A + a.Vd)) * sizeof(float) : 0;
   utt_split_finish_kernel<<<static_cast<unsigned>(a.N), kNT, lds, stream>>>(a, q, part);
@@ -2860,7 +2849,7 @@ extern "C" int mmb_mm2_stream_split(const int32_t* ids, const float* table, int6
     return MMB_OK;
   }
   const int P = parts > 0 ? std::min(parts, t) : mmb_mm2_stream_split_parts(n, t);
-  const SplitPlan q = split_plan_of(t, d, a_, vd, P, parts > 0 ? 1 : MMB_SPLIT_TEXT_X);
+  const SplitPlan q = split_plan_of(t, d, a_, vd, P, parts > 0 ? 1 : kSplitTextX);
   MMB_REQUIRE(ws && ws_bytes >= split_ws_floats(n, q) * sizeof(float));
   MMB_REQUIRE(n * (q.Pt + 2 * q.Pf) <= (int64_t{1} << 31) - 1);
   MMB_REQUIRE(3 * d + 2 * a_ + 2 * vd <= kSplitJ * kNT);  // the finish kernel's columns
@@ -3006,28 +2995,13 @@ namespace mmb {
 //     the division by the total weight (column D) and the L2 norm, the MMB2
 //     row written with 16-byte stores.
 // LDS: hot E rows 38.4 KB + hot P rows 38.9 KB + T 38.9 KB + A 32 KB.
-#ifndef NF_UNR
-#define NF_UNR 2
-#endif
-#ifndef NF_HU
-#define NF_HU 1
-#endif
-#ifndef NF_ABL  // timing-only ablations (tools/ab_libs): 1 no MFMA, 2 no frames, 4 no text,
-                // 8 no a2 / aux stores, 16 no MMB2 stores, 32 no id / weight loads
-#define NF_ABL 0
-#endif
-#ifndef NF_GA  // audio / visual frame loads issued with the text loads
-#define NF_GA 7
-#endif
-#ifndef NF_GV
-#define NF_GV 4
-#endif
-#ifndef NF_WAVES  // 8 (2 per SIMD, 32-row batches) or 12 (3 per SIMD, 36-row batches)
-#define NF_WAVES 8
-#endif
-constexpr int kNFWaves = NF_WAVES;
+constexpr int kNFUnr = 2;  // cold words per load group
+constexpr int kNFHU = 1;   // hot words per LDS group
+constexpr int kNFGA = 7;   // audio / visual frame loads issued with the text loads
+constexpr int kNFGV = 4;
+constexpr int kNFWaves = 8;  // 2 per SIMD, 32-row batches
 constexpr int kNFThreads = kNFWaves * kWave;
-constexpr int kNFRpw = kNFWaves == 8 ? 4 : 3;  // utterances per wave and batch (at most)
+constexpr int kNFRpw = 4;                   // utterances per wave and batch (at most)
 constexpr int kNFRows = kNFWaves * kNFRpw;     // rows of a batch (at most)
 constexpr int kNFRT = (kNFRows + 15) / 16;     // MFMA row tiles
 constexpr int kNFHot = 32;                  // = mm2_kernels.hip kTextHot
@@ -3040,9 +3014,8 @@ constexpr int kNFCT = kNFLdp / 16;          // 16-column tiles of y and the tota
 constexpr size_t kNFLdsRows = sizeof(float) * (kNFHot * kNFHotRow + kNFRows * kNFLdp) +
                               sizeof(_Float16) * kNFRows * 2 * kNFK + sizeof(float) * 3 * kNFRows;
 static_assert(kNFLdsRows % 16 == 0, "the frame-slot scratch is float4-aligned");
-// + 1 KB per wave for the frame-slot sums (12 waves: the utterance's own T
-// row, free until T is written, holds them instead)
-constexpr size_t kNFLds = kNFLdsRows + (kNFWaves == 8 ? 16 * kWave * kNFWaves : 0) + 16;  // + team counters
+// + 1 KB per wave for the frame-slot sums
+constexpr size_t kNFLds = kNFLdsRows + 16 * kWave * kNFWaves + 16;  // + team counters
 
 struct NarrowFusedArgs {
   StreamArgs s;        // ids, table, V, wtab, audio, visual, N, L, D, A, Vd, num_out, aux_out, flag, cmax_part
@@ -3068,7 +3041,7 @@ struct NarrowFusedArgs {
 template <int UNR, int HU, int GA_MAX, int GV_MAX, bool TM = false>
 __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFWaves / 4, kNFWaves / 4))) void utt_narrow_fused_kernel(
     NarrowFusedArgs f) {
-  static_assert(!TM || kNFWaves == 8, "teams of 4 waves: 8-wave workgroups");
+  static_assert(kNFWaves == 8, "teams of 4 waves: 8-wave workgroups");
   extern __shared__ __attribute__((aligned(16))) float nf_lds[];
   float* hotEP = nf_lds;                                  // [kNFHot][kNFHotRow]: E | P
   float* sT = hotEP + kNFHot * kNFHotRow;                 // [rows][kNFLdp]
@@ -3077,7 +3050,7 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
   float* s_cnt = s_irs + kNFRows;                         // [rows]
   float* s_ok = s_cnt + kNFRows;                          // [rows] 1 = a row of this batch
   float4* s_scr = reinterpret_cast<float4*>(s_ok + kNFRows);  // [waves][64] frame-slot sums
-  unsigned* s_team = reinterpret_cast<unsigned*>(s_scr + (kNFWaves == 8 ? kWave * kNFWaves : 0));  // [2]
+  unsigned* s_team = reinterpret_cast<unsigned*>(s_scr + kWave * kNFWaves);  // [2]
 
   const StreamArgs& a = f.s;
   // (holding these pointers in VGPRs instead -- fewer SGPR spills -- measured
@@ -3164,16 +3137,13 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
     }
   };
   auto ld_id = [&](int i) -> int {
-    if (NF_ABL & 32) return (i < N && lane < L) ? (lane * 131 + i) % V : -1;
     return (i < N && lane < L) ? ids_v[static_cast<int64_t>(i) * L + lane] : -1;
   };
   auto resolve = [&](int raw, int& rid, float& w, int& hs) {
     rid = -1;
     w = 0.f;
     hs = 0;
-    if (NF_ABL & 32) {
-      if (raw >= 0) rid = raw, w = 1.f;
-    } else if (lane < L) {
+    if (lane < L) {
       int id = raw;
       const bool in = id >= 0 && id < V;
       w = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(prsrc, in ? wbase + id * 4 : cbytes, 0, 0));
@@ -3282,9 +3252,8 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
       };
       using GAc = std::integral_constant<int, GA_MAX>;
       using GVc = std::integral_constant<int, GV_MAX>;
-      using G0 = std::integral_constant<int, 0>;
-      auto acc_a = frames(std::conditional_t<(NF_ABL & 2) != 0, G0, GAc>{}, arsrc, voa, a.A, UA, PA, 0, sa, saa);
-      auto acc_v = frames(std::conditional_t<(NF_ABL & 2) != 0, G0, GVc>{}, vrsrc, vov, a.Vd, UV, PV, 0, sv, svv);
+      auto acc_a = frames(GAc{}, arsrc, voa, a.A, UA, PA, 0, sa, saa);
+      auto acc_v = frames(GVc{}, vrsrc, vov, a.Vd, UV, PV, 0, sv, svv);
 
       // text: the x sums (w E) and the P rows of the text term over the
       // utterance's valid tokens -- hot words (LDS) while the first group of
@@ -3295,8 +3264,8 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
 #pragma unroll
       for (int c = 0; c < CQ; ++c) ac[c] = z4;
       const bool tok = lane < L && rid >= 0;
-      uint64_t cold = (NF_ABL & 4) ? 0 : __builtin_amdgcn_ballot_w64(tok && hs == 0);
-      uint64_t hot = (NF_ABL & 4) ? 0 : __builtin_amdgcn_ballot_w64(tok && hs > 0);
+      uint64_t cold = __builtin_amdgcn_ballot_w64(tok && hs == 0);
+      uint64_t hot = __builtin_amdgcn_ballot_w64(tok && hs > 0);
       auto cold_row = [&](int t, float4 (&v)[CQ]) {
         const int rr = t >= 0 ? __builtin_amdgcn_readlane(rid, t) : -1;
         const int so = rr >= 0 ? rr * kNFLdq * 4 : cbytes;  // none: out of range, reads 0
@@ -3356,7 +3325,7 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
       // `lane`): each frame sum's P row slots added up through this wave's 1
       // KB of LDS (one write, P reads by the lanes holding that piece; slot 0
       // first, as the shuffle reduction of utt_narrow_kernel); pads 0
-      float4* scr = kNFWaves == 8 ? s_scr + wave * kWave : reinterpret_cast<float4*>(sT + r * kNFLdp);
+      float4* scr = s_scr + wave * kWave;
       float4 av = z4;
       auto gather = [&](const float4& acc, int U, int P, int u0) {
         __builtin_amdgcn_wave_barrier();  // the previous piece's reads are issued
@@ -3398,7 +3367,7 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
         if (uu < UT) {
           const float4 xr = make_float4(ac[c].x * rc, ac[c].y * rc, ac[c].z * rc, ac[c].w * rc);
           if (live) {
-            if (!(NF_ABL & 8)) st4(num_out + static_cast<int64_t>(i) * D + 4 * uu, xr);
+            st4(num_out + static_cast<int64_t>(i) * D + 4 * uu, xr);
             cmx[c] = bmax4(cmx[c], xr);
           }
           float4 tv = *reinterpret_cast<const float4*>(trow + 4 * uu);
@@ -3420,7 +3389,7 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
         s_irs[r] = 1.f / rsc;
         s_cnt[r] = cnt;
         s_ok[r] = live ? 1.f : 0.f;
-        if (live && !(NF_ABL & 8)) {
+        if (live) {
           aux_out[i] = cnt;
           aux_out[static_cast<int64_t>(N) + i] = sw;
           aux_out[2 * static_cast<int64_t>(N) + i] = rsc;
@@ -3438,7 +3407,7 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
       for (int rt = 0; rt < kTRT; ++rt)
 #pragma unroll
         for (int tt = 0; tt < kMaxT; ++tt) acc[rt][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int c = 0; c < ((NF_ABL & 1) ? 0 : nch); ++c) {
+      for (int c = 0; c < nch; ++c) {
         half8 nh[kMaxT], nl[kMaxT];  // chunk c + 1, in flight during chunk c
         if (c + 1 < nch) ld_b(c + 1, nh, nl);
 #pragma unroll
@@ -3519,7 +3488,7 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
         if (uu < UT) ss += y[c].x * y[c].x + y[c].y * y[c].y + y[c].z * y[c].z + y[c].w * y[c].w;
       }
       const float inv = __builtin_amdgcn_rsqf(wave_sum_dpp_f32(ss));  // v_rsq_f32 (1 ulp)
-      if (s_ok[r] != 0.f && !(NF_ABL & 16)) {
+      if (s_ok[r] != 0.f) {
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
           const int uu = lane + kWave * c;
@@ -3598,13 +3567,12 @@ extern "C" int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* ta
 #define MMB_HOOK_NF_TEAMS 0
 #endif
   int teams = MMB_HOOK_NF_TEAMS;  // 1: two teams of 4 waves per workgroup, 2: the same, team 1 starting a phase later
-  if (kNFWaves != 8) teams = 0;
   f.team_lag = teams == 2 ? 1 : 0;
   // batches: of 8 rpw rows, or of 4 rpw rows per team (two per workgroup)
   f.nb = ceil_div(n, static_cast<int64_t>(teams ? kNFWaves / 2 : kNFWaves) * f.rpw);
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&utt_narrow_fused_kernel<NF_UNR, NF_HU, NF_GA, NF_GV>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kNFLds));
 #ifdef MMB_HOOK_NF_TEAMS_ATTR
     MMB_HOOK_NF_TEAMS_ATTR;
@@ -3618,7 +3586,7 @@ extern "C" int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* ta
 #define MMB_HOOK_NF_TEAMS_LAUNCH false
 #endif
   if (!(MMB_HOOK_NF_TEAMS_LAUNCH))
-    utt_narrow_fused_kernel<NF_UNR, NF_HU, NF_GA, NF_GV><<<static_cast<unsigned>(grid), kNFThreads, kNFLds, stream>>>(f);
+    utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV><<<static_cast<unsigned>(grid), kNFThreads, kNFLds, stream>>>(f);
   MMB_LAUNCH_CHECK();
   if (!colmax) return MMB_OK;
   colmax_reduce_kernel<<<static_cast<unsigned>(ceil_div(d, 64)), 1024, 0, stream>>>(

@@ -14,7 +14,7 @@ Data layout in HBM (one utterance per row, row-major, fp32 unless noted):
 """
 from __future__ import annotations
 
-import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -177,18 +177,6 @@ def xt_omega(num, cnt, omega_rows: torch.Tensor) -> torch.Tensor:
     return z0
 
 
-def pc_start_block(n_total: int, d: int, npc: int, device, num=None, cnt=None, row0: int = 0,
-                   n_total_rows_omega: int | None = None):
-    """Z0 of sklearn's randomized SVD.  Direct branch: Omega [d,k].  Transposed
-    branch (n_total < d): X^T Omega_n for this shard's rows [row0, row0+n)."""
-    check_npc(npc)
-    k = npc + N_OVERSAMPLES
-    if n_total >= d:
-        return omega(d, k, device), False
-    om = omega(n_total, k, device)[row0:row0 + num.shape[0]].contiguous()
-    return xt_omega(num, cnt, om), True
-
-
 PC_SOLVE_MC_MAX_D = 320  # mmb_pc_solve_mc: ceil(d / 16) workgroups, k <= 16
 _solve_ws: dict = {}
 
@@ -255,17 +243,19 @@ def pc_f64(x64: torch.Tensor, npc: int) -> torch.Tensor:
     drop-ins' general input): Gram, start block and solve all read f64 rows."""
     check_npc(npc)
     n, d = x64.shape
-    k = npc + N_OVERSAMPLES
     G = torch.empty((d, d), dtype=torch.float64, device=x64.device)
     ws = GramWorkspace(n, d, x64.device)
     L.call("mmb_gram_f64", L.ptr(x64), n, d, L.ptr(G), 0, L.ptr(ws.buf), L.stream_ptr())
-    if n >= d:
-        z0, transposed = omega(d, k, x64.device), False
-    else:
-        z0, transposed = torch.empty((d, k), dtype=torch.float64, device=x64.device), True
-        L.call("mmb_xt_omega_f64", L.ptr(x64), n, d, L.ptr(omega(n, k, x64.device)), k,
-               L.ptr(z0), L.stream_ptr())
+    z0, transposed = pc_start_block(x64, None, npc, n, ops=F64Ops)
     return pc_solve(G, z0, npc, transposed)
+
+
+def xt_omega_f64(x64, cnt, omega_rows: torch.Tensor) -> torch.Tensor:
+    n, d = x64.shape
+    k = omega_rows.shape[1]
+    z0 = torch.empty((d, k), dtype=torch.float64, device=x64.device)
+    L.call("mmb_xt_omega_f64", L.ptr(x64), n, d, L.ptr(omega_rows), k, L.ptr(z0), L.stream_ptr())
+    return z0
 
 
 def remove_pc_f64(x64: torch.Tensor, pc: torch.Tensor) -> torch.Tensor:
@@ -285,6 +275,26 @@ class DeviceOps:
     pc_solve = staticmethod(pc_solve)
 
 
+class F64Ops(DeviceOps):
+    """The start block of pc_f64: X^T Omega from float64 rows."""
+
+    xt_omega = staticmethod(xt_omega_f64)
+
+
+def pc_start_block(num, cnt, npc: int, n_total: int, row0: int = 0, ops=DeviceOps):
+    """(Z0, transposed) of sklearn's randomized SVD from this rank's rows
+    [row0, row0 + n) of X = num / cnt.  Direct branch: Omega [d, k].
+    Transposed branch (n_total < d): X^T Omega_n over Omega's rows of this
+    shard."""
+    check_npc(npc)
+    n, d = num.shape
+    k = npc + N_OVERSAMPLES
+    if n_total >= d:
+        return ops.omega(d, k, num.device), False
+    om = ops.omega(n_total, k, num.device)[row0:row0 + n].contiguous()
+    return ops.xt_omega(num, cnt, om), True
+
+
 def global_pc(num, cnt, npc: int, n_total: int, row0: int = 0, allreduce=None, ops=DeviceOps,
               G=None, ws=None):
     """The PC of ALL utterances across ranks (a3), from this rank's rows
@@ -295,15 +305,9 @@ def global_pc(num, cnt, npc: int, n_total: int, row0: int = 0, allreduce=None, o
     ranks, each as one all-reduce (sum).  Every rank then runs the same
     deterministic solve, so the PC is identical everywhere with no broadcast.
     """
-    n, d = num.shape
     check_npc(npc)
-    k = npc + N_OVERSAMPLES
     G = ops.gram(num, cnt, G, ws)
-    if n_total >= d:
-        z0, transposed = ops.omega(d, k, num.device), False
-    else:
-        om = ops.omega(n_total, k, num.device)[row0:row0 + n].contiguous()
-        z0, transposed = ops.xt_omega(num, cnt, om), True
+    z0, transposed = pc_start_block(num, cnt, npc, n_total, row0, ops)
     if allreduce is not None:
         allreduce(G)
         if transposed:
@@ -619,14 +623,14 @@ def mm2_project(s, num, aux, proj: MMB2Projection, out=None, pc=None, sif_out=No
     n = num.shape[0]
     if out is None:
         out = torch.empty((n, proj.d), dtype=torch.float32, device=num.device)
+    if pc is not None and (s.dtype != torch.float16 or pc.shape[0] != 1 or sif_out is None):
+        raise L.MMBError("fused PC removal needs fp16 s, npc = 1 and sif_out")
     if split is not None and s.dtype == torch.float16:
         L.call("mmb_mm2_project_x3_split", L.ptr(s), L.ptr(num), L.ptr(aux), L.ptr(proj.wsplit),
                proj.ldw, L.ptr(proj.c0), n, proj.kp, proj.d, L.ptr(out), L.ptr(pc),
                L.ptr(sif_out), int(slices), L.ptr(split), split.numel(), L.stream_ptr())
         return out
     if pc is not None:
-        if s.dtype != torch.float16 or pc.shape[0] != 1 or sif_out is None:
-            raise L.MMBError("fused PC removal needs fp16 s, npc = 1 and sif_out")
         L.call("mmb_mm2_project_x3_rmpc", L.ptr(s), L.ptr(num), L.ptr(aux), L.ptr(proj.wsplit),
                proj.ldw, L.ptr(proj.c0), n, proj.kp, proj.d, L.ptr(out), L.ptr(pc),
                L.ptr(sif_out), L.stream_ptr())
@@ -703,6 +707,95 @@ GRAM_I8_MIN_ROWS = 1 << 15
 FORK_PROJECTION_MAX_ROWS = 4096
 
 
+class StepPlan(NamedTuple):
+    """What one FusedStep launches, decided once from shapes (step_plan)."""
+
+    front: str        # writes x, aux: "narrow_fused" / "fused" (and mmb2) or "stream" (and s)
+    split: bool       # the stream kernel over several workgroups per utterance
+    gram: str         # "i8", "f64", or "parts" (per-chunk partials + mmb_gram_finish)
+    project: str      # where the projection runs: "front" (inside the front kernel), "fork"
+                      # (beside Gram -> solve), "remove" (after the solve, one kernel with
+                      # the removal) or "chunk" (with each chunk's Gram)
+    proj_split: bool  # the projection may run split-K (a few rows)
+    bounds: tuple     # row chunks ((r0, r1), ...)
+    step_rows: int    # rows of a full chunk
+    s_half: bool      # s as fp16 hi | lo planes (the x3 projection)
+
+    @property
+    def remove_launch(self) -> bool:
+        """The removal is its own launch (mmb_pc_remove)."""
+        return self.project != "remove"
+
+
+def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc: int, cus: int,
+              chunks: int | None = None, fuse_remove: bool = True, gram_kind: str | None = None,
+              stream_project: bool | None = None, narrow_fused: bool | None = None,
+              fork_projection: bool | None = None, split_stream: bool | None = None,
+              split_projection: bool = True) -> StepPlan:
+    """The plan of a step over `n` of a split's `n_total` utterances on a chip
+    of `cus` CUs; the remaining arguments are FusedStep's overrides (None: by
+    shape).  Precedence: the fused front kernels need one chunk ASKED for and
+    the fp16 split, the wide-frame one first; fewer utterances than features
+    force one chunk (the transposed branch needs X^T Omega of all rows); the
+    projection forks or takes the removal only behind the plain stream kernel,
+    in one chunk, at npc = 1."""
+    check_npc(npc)
+    s_half = L.query("mmb_mm2_ldw", d) <= 320
+    one_asked = (chunks or 1) == 1
+    if stream_project is None:
+        stream_project = fused_pays(a, vd)
+    if narrow_fused is None:
+        narrow_fused = True
+    if stream_project and one_asked and s_half and stream_project_supported(t, d, a, vd):
+        front = "fused"
+    elif narrow_fused and one_asked and s_half and narrow_fused_supported(t, d, a, vd, V):
+        front = "narrow_fused"
+    else:
+        front = "stream"
+    if chunks is None or n_total < d:
+        chunks = 1
+    chunks = max(1, min(chunks, n))
+    step = -(-n // chunks)
+    step = -(-step // 256) * 256  # 16-byte aligned chunk starts (two-phase Gram)
+    bounds = tuple((r, min(r + step, n)) for r in range(0, n, step)) or ((0, 0),)
+    one = len(bounds) == 1
+    # Gram of the one-chunk step: "i8" (mmb_gram_i8, int8 digits of the
+    # column-bounded fixed-point x, ~1e-10 of exact; the bounds come from
+    # the front kernel) or "f64" (mmb_gram, exact f64 products)
+    if gram_kind is None:
+        gram_kind = "i8" if n_total >= GRAM_I8_MIN_ROWS else "f64"
+    if gram_kind not in ("i8", "f64"):
+        raise ValueError(f"gram_kind must be 'i8' or 'f64', not {gram_kind!r}")
+    if not one:
+        gram = "parts" if d % 4 == 0 and d <= 320 else "f64"
+    else:
+        gram = "i8" if gram_kind == "i8" and d % 4 == 0 and d <= 304 else "f64"
+    # small steps (the dataset splits): the projection runs on a forked
+    # stream beside the Gram -> PC solve chain, and the removal is its own
+    # small launch, instead of the projection waiting for the PC to fuse
+    # the removal into its tail (that saves an HBM pass only at scale)
+    if fork_projection is None:
+        fork_projection = n <= FORK_PROJECTION_MAX_ROWS
+    if front != "stream":
+        project = "front"
+    elif fuse_remove and one and npc == 1 and s_half:
+        project = "fork" if fork_projection else "remove"
+    else:
+        project = "chunk"
+    # a few long rows (POM's splits): every utterance's tokens and each
+    # modality's frames on workgroups of their own (mmb_mm2_stream_split),
+    # so 100-203 rows fill the chip instead of one workgroup each
+    split = bool((split_stream is None or split_stream) and front == "stream" and one
+                 and t > 64 and 0 < n <= cus)
+    proj_split = bool(split_projection and front == "stream" and s_half and one)
+    return StepPlan(front, split, gram, project, proj_split, bounds, step, s_half)
+
+
+# the fused front kernels: trace phase and mirror
+_FRONTS = {"fused": ("mm2_stream_project", mm2_stream_project),
+           "narrow_fused": ("mm2_stream_project_narrow", mm2_stream_project_narrow)}
+
+
 class FusedStep:
     """One pass of the north-star hot path over a batch of utterances resident
     in HBM (bench 'step'): both the SIF text embedding (a1-a5, PC-removed) and
@@ -745,6 +838,11 @@ class FusedStep:
     f32 order than the one-pass kernel), and `fork_projection` runs it on a
     side stream beside Gram -> PC solve; each is chosen by shape when left at
     its default.
+
+    Which of these a step takes is decided once, by step_plan() (`self.plan`);
+    _run is one sequence over it: front kernel, chunk pipeline, projection
+    (unless the front kernel or the removal carries it), Gram, PC solve,
+    removal.
     """
 
     def __init__(self, inputs: dict, networks: dict, npc: int = 1, allreduce=None,
@@ -763,32 +861,22 @@ class FusedStep:
         self.a = inputs["audio"].shape[-1]
         self.vd = inputs["visual"].shape[-1]
         dev = self.table.device
+        self.npc = npc
+        self.allreduce = allreduce
+        self.n_total = self.n if n_total is None else n_total
+        self.row0 = row0
+        self.plan = p = step_plan(self.n, self.n_total, self.t, self.d, self.a, self.vd, self.V, npc,
+                                  L.cu_count(dev), chunks=chunks, fuse_remove=fuse_remove,
+                                  gram_kind=gram_kind, stream_project=stream_project,
+                                  narrow_fused=narrow_fused, fork_projection=fork_projection,
+                                  split_stream=split_stream, split_projection=split_projection)
         self.proj = MMB2Projection(networks, self.d, self.a, self.vd, self.t, dev)
         kp = self.proj.kp
         self.x = torch.empty((self.n, self.d), dtype=torch.float32, device=dev)
-        self.s_half = x3_supported(self.proj)
-        # stream + projection in one kernel (s never in HBM): one chunk, the
-        # shapes the kernel takes, and wide frames (fused_pays);
-        # MMB_STREAM_PROJECT=0 / 1 forces the two kernels / the fused one
-        if stream_project is None:
-            env = os.environ.get("MMB_STREAM_PROJECT")
-            stream_project = fused_pays(self.a, self.vd) if env is None else env != "0"
-        self.stream_project = (bool(stream_project) and (chunks or 1) == 1 and self.s_half
-                               and stream_project_supported(self.t, self.d, self.a, self.vd))
-        # narrow frame widths (MOSI): stream and projection in ONE kernel with
-        # the per-word text cache (mmb_mm2_stream_project_narrow), one chunk;
-        # MMB_NARROW_FUSED=0 / 1 forces the two kernels / the fused one
-        if narrow_fused is None:
-            env = os.environ.get("MMB_NARROW_FUSED")
-            narrow_fused = True if env is None else env != "0"
-        self.narrow_fused = (bool(narrow_fused) and not self.stream_project and (chunks or 1) == 1
-                             and self.s_half
-                             and narrow_fused_supported(self.t, self.d, self.a, self.vd, self.V))
-        self.s = (None if (self.stream_project or self.narrow_fused)
-                  else s_buffer(self.n, kp, self.s_half, dev))
-        if self.stream_project:
+        self.s = s_buffer(self.n, kp, p.s_half, dev) if p.front == "stream" else None
+        if p.front == "fused":
             self.proj.enable_pieces()
-        if self.narrow_fused:
+        if p.front == "narrow_fused":
             self.proj.enable_text_cache(self.table, inputs["wtab"])
         self.G = torch.empty((self.d, self.d), dtype=torch.float64, device=dev)
         self.pc_buf = torch.empty((npc, self.d), dtype=torch.float64, device=dev)
@@ -796,69 +884,24 @@ class FusedStep:
                                      device=dev) if self.d <= PC_SOLVE_MC_MAX_D else None)
         self.sif = torch.empty((self.n, self.d), dtype=torch.float32, device=dev)
         self.mmb2 = torch.empty((self.n, self.d), dtype=torch.float32, device=dev)
-        check_npc(npc)
-        self.npc = npc
-        self.allreduce = allreduce
-        self.n_total = self.n if n_total is None else n_total
-        self.row0 = row0
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        if chunks is None:
-            chunks = 1
-        if self.n_total < self.d:  # sklearn's transposed branch needs X^T Omega of all rows
-            chunks = 1
-        chunks = max(1, min(chunks, self.n))
-        step = -(-self.n // chunks)
-        step = -(-step // 256) * 256  # 16-byte aligned chunk starts (two-phase Gram)
-        self.bounds = [(r, min(r + step, self.n)) for r in range(0, self.n, step)] or [(0, 0)]
-        self.step_rows = step
         # aux is planar per chunk: chunk [r0, r1) owns flat[3 r0 : 3 r1] as [3][r1 - r0]
         self.aux_flat = torch.empty((3 * self.n,), dtype=torch.float32, device=dev)
-        self.gram_parts = len(self.bounds) > 1 and self.d % 4 == 0 and self.d <= 320
-        self.fused_remove = (fuse_remove and len(self.bounds) == 1 and npc == 1 and self.s_half
-                             and not self.narrow_fused)
-        # Gram of the one-chunk step: "i8" (mmb_gram_i8, int8 digits of the
-        # column-bounded fixed-point x, ~1e-10 of exact; the bounds come from
-        # the stream kernel) or "f64" (mmb_gram, exact f64 products).
-        # MMB_GRAM overrides the default (A/B runs).
-        if gram_kind is None:
-            gram_kind = os.environ.get("MMB_GRAM", "i8" if self.n_total >= GRAM_I8_MIN_ROWS
-                                       else "f64")
-        if gram_kind not in ("i8", "f64"):
-            raise ValueError(f"gram_kind must be 'i8' or 'f64', not {gram_kind!r}")
-        self.gram_i8 = (gram_kind == "i8" and len(self.bounds) == 1 and self.d % 4 == 0
-                        and self.d <= 304)
-        if self.gram_i8:
+        if p.gram == "i8":
             self.colmax = torch.zeros((self.d,), dtype=torch.int32, device=dev)
             nb = L.query("mmb_mm2_colmax_ws_bytes", self.d)
             self.colmax_ws = torch.empty((nb + 15) // 16 * 16, dtype=torch.uint8, device=dev)
         else:
             self.colmax = self.colmax_ws = None
-        # a few long rows (POM's splits): every utterance's tokens and each
-        # modality's frames on workgroups of their own (mmb_mm2_stream_split),
-        # so 100-203 rows fill the chip instead of one workgroup each
-        self.split = None
-        if split_stream is None:
-            split_stream = True
-        if (split_stream and not self.stream_project and not self.narrow_fused
-                and len(self.bounds) == 1
-                and self.t > 64 and 0 < self.n <= L.cu_count(dev)):
-            self.split = split_ws(self.n, self.t, self.d, self.a, self.vd, dev)
-        # small steps (the dataset splits): the projection runs on a forked
-        # stream beside the Gram -> PC solve chain, and the removal is its own
-        # small launch, instead of the projection waiting for the PC to fuse
-        # the removal into its tail (that saves an HBM pass only at scale)
-        if fork_projection is None:
-            fork_projection = self.n <= FORK_PROJECTION_MAX_ROWS
-        self.fork = torch.cuda.Stream(device=dev) if self.fused_remove and fork_projection else None
-        # a few rows: the projection's K loop split over workgroups
-        self.proj_split = (project_split_ws(self.n, kp, dev)
-                           if split_projection and self.s is not None and self.s_half
-                           and len(self.bounds) == 1 else None)
-        self.gws = GramWorkspace(max(r1 - r0 for r0, r1 in self.bounds), self.d, dev)
-        self.side = torch.cuda.Stream(device=dev) if len(self.bounds) > 1 else None
+        self.split = split_ws(self.n, self.t, self.d, self.a, self.vd, dev) if p.split else None
+        self.fork = torch.cuda.Stream(device=dev) if p.project == "fork" else None
+        # (None where the rows alone fill the chip)
+        self.proj_split = project_split_ws(self.n, kp, dev) if p.proj_split else None
+        self.gws = GramWorkspace(max(r1 - r0 for r0, r1 in p.bounds), self.d, dev)
+        self.side = torch.cuda.Stream(device=dev) if len(p.bounds) > 1 else None
         self.main = None
         self._cu_streams = []
-        self._events = [torch.cuda.Event() for _ in self.bounds]
+        self._events = [torch.cuda.Event() for _ in p.bounds]
         if side_cus and self.side is not None:
             # disjoint CU sets: the stream kernel on `main`, the projection +
             # Gram of the previous chunk on `side`
@@ -867,6 +910,16 @@ class FusedStep:
             main_set = [c for c in range(n_cu) if c not in set(side_set)]
             self._cu_streams = [L.CUStream(main_set, dev), L.CUStream(side_set, dev)]
             self.main, self.side = self._cu_streams[0].torch, self._cu_streams[1].torch
+
+    # the plan, under the names the step has always answered to
+    stream_project = property(lambda self: self.plan.front == "fused")
+    narrow_fused = property(lambda self: self.plan.front == "narrow_fused")
+    gram_i8 = property(lambda self: self.plan.gram == "i8")
+    gram_parts = property(lambda self: self.plan.gram == "parts")
+    fused_remove = property(lambda self: not self.plan.remove_launch)
+    bounds = property(lambda self: self.plan.bounds)
+    step_rows = property(lambda self: self.plan.step_rows)
+    s_half = property(lambda self: self.plan.s_half)
 
     def check(self):
         """Raise what the reference would have raised for the last step(s):
@@ -940,11 +993,16 @@ class FusedStep:
                    out=(self.x[r0:r1], self.s[r0:r1], self.aux_of(c)),
                    colmax=self.colmax, colmax_ws=self.colmax_ws, split=self.split)
 
-    def _consume_chunk(self, c: int):
+    def _project(self, c: int, pc=None):
+        """Chunk c's MMB2 rows; with `pc` also its PC-removed rows."""
         r0, r1 = self.bounds[c]
-        aux = self.aux_of(c)
-        mm2_project(self.s[r0:r1], self.x[r0:r1], aux, self.proj, out=self.mmb2[r0:r1],
+        mm2_project(self.s[r0:r1], self.x[r0:r1], self.aux_of(c), self.proj, out=self.mmb2[r0:r1],
+                    pc=pc, sif_out=None if pc is None else self.sif[r0:r1],
                     split=self.proj_split)  # (None past one chunk)
+
+    def _gram(self, c: int):
+        """Chunk c's rows into G (or into the partials of mmb_gram_finish)."""
+        r0, r1 = self.bounds[c]
         if self.gram_parts:
             L.call("mmb_gram_part", L.ptr(self.x[r0:r1]), None, r1 - r0,
                    self.step_rows, self.d, int(c > 0), L.ptr(self.gws.buf), L.stream_ptr())
@@ -953,13 +1011,42 @@ class FusedStep:
         else:
             gram(self.x[r0:r1], None, self.G, accumulate=c > 0, ws=self.gws)
 
-    def _solve(self, trace, mark):
+    def _pipeline_chunks(self, mark):
+        """Chunks 1 .. nb-1 streamed on `main` while the chunk before each is
+        projected and its Gram partial formed on `side`; chunk 0 is streamed
+        and the last chunk is left to the caller's stream."""
+        nb = len(self.bounds)
+        caller = torch.cuda.current_stream(self.table.device)
+        main = self.main if self.main is not None else caller
+        side = self.side
+        ev = self._events
+        ev[0].record(caller)
+        if main is not caller:
+            main.wait_stream(caller)
+        side.wait_stream(caller)
+        for c in range(1, nb):
+            with torch.cuda.stream(main):
+                with mark("mm2_stream"):
+                    self._stream_chunk(c)
+                if c < nb - 1:
+                    ev[c].record(main)
+            with torch.cuda.stream(side):
+                side.wait_event(ev[c - 1])
+                with mark("mm2_project+gram"):
+                    self._project(c - 1)
+                    self._gram(c - 1)
+        if main is not caller:
+            caller.wait_stream(main)
+        caller.wait_stream(side)
+
+    def _solve(self, mark):
         """G (this rank's rows) -> pc: Omega, RCCL all-reduce of G, the solve."""
         d, k = self.d, self.npc + N_OVERSAMPLES
-        if (self.n_total < d and self.allreduce is None and self.solve_ws is not None
-                and k <= 16):
-            # the transposed branch, unsharded: X^T Omega and the squared
-            # matrix in one launch in front of the solve (mmb_pc_solve_mc_xt)
+        if (self.n_total < d and self.allreduce is None and self.row0 == 0
+                and self.n_total == self.n and self.solve_ws is not None and k <= 16):
+            # the transposed branch over all of Omega's rows, unsharded: X^T
+            # Omega and the squared matrix in one launch in front of the
+            # solve (mmb_pc_solve_mc_xt)
             om = omega(self.n_total, k, self.table.device)
             with mark("pc_solve"):
                 L.call("mmb_pc_solve_mc_xt", L.ptr(self.G), d, L.ptr(self.x), self.n, L.ptr(om), k,
@@ -967,11 +1054,7 @@ class FusedStep:
                        L.stream_ptr())
             return self.pc_buf
         with mark("pc_start"):
-            if self.n_total >= d:
-                z0, transposed = omega(d, k, self.table.device), False
-            else:
-                om = omega(self.n_total, k, self.table.device)[self.row0:self.row0 + self.n]
-                z0, transposed = xt_omega(self.x, None, om.contiguous()), True
+            z0, transposed = pc_start_block(self.x, None, self.npc, self.n_total, self.row0)
         if self.allreduce is not None:
             with mark("allreduce"):
                 self.allreduce(self.G)
@@ -1000,49 +1083,24 @@ class FusedStep:
                 return _NullSpan()
             return _EventSpan(trace.setdefault(name, []))
 
-        d, k = self.d, self.npc + N_OVERSAMPLES
-        nb = len(self.bounds)
+        p = self.plan
+        last = len(p.bounds) - 1
         with mark("mm2_prepare"):
             self.proj.refresh_if_changed()
-        if self.narrow_fused:
-            inp = self.inp
-            with mark("mm2_stream_project_narrow"):
-                mm2_stream_project_narrow(self.n, self.t, self.d, self.a, self.vd, inp["audio"],
-                                          inp["visual"], self.proj, self.ids, self.table,
-                                          inp["wtab"], flag=self.flag,
-                                          out=(self.x, self.aux_of(0), self.mmb2),
-                                          colmax=self.colmax, colmax_ws=self.colmax_ws)
-            with mark("gram"):
-                if self.gram_i8:
-                    gram_i8(self.x, self.colmax, self.G, ws=self.gws)
-                else:
-                    gram(self.x, None, self.G, ws=self.gws)
-            pc = self._solve(trace, mark)
-            with mark("pc_remove"):
-                remove_pc(self.x, None, pc, out=self.sif)
-            self.pc = pc
-            return self.sif, self.mmb2
-        if self.stream_project:
-            inp = self.inp
-            with mark("mm2_stream_project"):
-                mm2_stream_project(self.n, self.t, self.d, self.a, self.vd, inp["audio"],
-                                   inp["visual"], self.proj, ids32=self.ids, table=self.table,
-                                   wtab32=inp["wtab"], flag=self.flag,
-                                   out=(self.x, self.aux_of(0), self.mmb2), colmax=self.colmax,
-                                   colmax_ws=self.colmax_ws)
-            with mark("gram"):
-                if self.gram_i8:
-                    gram_i8(self.x, self.colmax, self.G, ws=self.gws)
-                else:
-                    gram(self.x, None, self.G, ws=self.gws)
-            pc = self._solve(trace, mark)
-            with mark("pc_remove"):
-                remove_pc(self.x, None, pc, out=self.sif)
-            self.pc = pc
-            return self.sif, self.mmb2
-        with mark("mm2_stream"):
-            self._stream_chunk(0)  # every CU
-        if self.fork is not None:
+        if p.front == "stream":
+            with mark("mm2_stream"):
+                self._stream_chunk(0)  # every CU
+        else:
+            phase, front = _FRONTS[p.front]
+            with mark(phase):
+                front(self.n, self.t, self.d, self.a, self.vd, self.inp["audio"],
+                      self.inp["visual"], self.proj, ids32=self.ids, table=self.table,
+                      wtab32=self.inp["wtab"], flag=self.flag,
+                      out=(self.x, self.aux_of(0), self.mmb2), colmax=self.colmax,
+                      colmax_ws=self.colmax_ws)
+        if last > 0:
+            self._pipeline_chunks(mark)
+        if p.project == "fork":
             # the projection beside the Gram -> solve chain; with fork=False
             # (inside a concurrent StepGraph) the same kernels in one stream,
             # so the rows are the forked step's bit for bit
@@ -1052,64 +1110,25 @@ class FusedStep:
                 side.wait_stream(caller)
             with torch.cuda.stream(side):
                 with mark("mm2_project"):
-                    mm2_project(self.s, self.x, self.aux_of(0), self.proj, out=self.mmb2,
-                                split=self.proj_split)
-            with mark("gram"):
-                if self.gram_i8:
-                    gram_i8(self.x, self.colmax, self.G, ws=self.gws)
-                else:
-                    gram(self.x, None, self.G, ws=self.gws)
-            pc = self._solve(trace, mark)
-            with mark("pc_remove"):
-                remove_pc(self.x, None, pc, out=self.sif)
-            if fork:
-                caller.wait_stream(side)
-            self.pc = pc
-            return self.sif, self.mmb2
-        if self.fused_remove:
-            with mark("gram"):
-                if self.gram_i8:
-                    gram_i8(self.x, self.colmax, self.G, ws=self.gws)
-                else:
-                    gram(self.x, None, self.G, ws=self.gws)
-            pc = self._solve(trace, mark)
-            with mark("mm2_project+pc_remove"):
-                mm2_project(self.s, self.x, self.aux_of(0), self.proj, out=self.mmb2, pc=pc,
-                            sif_out=self.sif, split=self.proj_split)
-            self.pc = pc
-            return self.sif, self.mmb2
-        if nb > 1:
-            caller = torch.cuda.current_stream(self.table.device)
-            main = self.main if self.main is not None else caller
-            side = self.side
-            ev = self._events
-            ev[0].record(caller)
-            if main is not caller:
-                main.wait_stream(caller)
-            side.wait_stream(caller)
-            for c in range(1, nb):
-                with torch.cuda.stream(main):
-                    with mark("mm2_stream"):
-                        self._stream_chunk(c)
-                    if c < nb - 1:
-                        ev[c].record(main)
-                with torch.cuda.stream(side):
-                    side.wait_event(ev[c - 1])
-                    with mark("mm2_project+gram"):
-                        self._consume_chunk(c - 1)
-            if main is not caller:
-                caller.wait_stream(main)
-            caller.wait_stream(side)
-        with mark("mm2_project+gram"):
-            self._consume_chunk(nb - 1)  # every CU
-        if self.gram_parts:
+                    self._project(0)
+        with mark("mm2_project+gram" if p.project == "chunk" else "gram"):
+            if p.project == "chunk":
+                self._project(last)  # every CU
+            self._gram(last)
+        if p.gram == "parts":
             with mark("gram_finish"):
-                L.call("mmb_gram_finish", self.step_rows, d, L.ptr(self.G), 0, L.ptr(self.gws.buf),
-                       L.stream_ptr())
-        pc = self._solve(trace, mark)
-        with mark("pc_remove"):
-            for c, (r0, r1) in enumerate(self.bounds):
-                remove_pc(self.x[r0:r1], None, pc, out=self.sif[r0:r1])
+                L.call("mmb_gram_finish", p.step_rows, self.d, L.ptr(self.G), 0,
+                       L.ptr(self.gws.buf), L.stream_ptr())
+        pc = self._solve(mark)
+        if p.remove_launch:
+            with mark("pc_remove"):
+                for r0, r1 in p.bounds:
+                    remove_pc(self.x[r0:r1], None, pc, out=self.sif[r0:r1])
+        else:
+            with mark("mm2_project+pc_remove"):
+                self._project(0, pc=pc)
+        if p.project == "fork" and fork:
+            caller.wait_stream(side)
         self.pc = pc
         return self.sif, self.mmb2
 

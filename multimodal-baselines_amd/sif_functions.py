@@ -98,7 +98,7 @@ def _pc_device(x, npc):
     if x.dtype == torch.float64:
         return P.pc_f64(x, npc)
     G = P.gram(x, None)
-    z0, transposed = P.pc_start_block(x.shape[0], x.shape[1], npc, x.device, x, None)
+    z0, transposed = P.pc_start_block(x, None, npc, x.shape[0])
     return P.pc_solve(G, z0, npc, transposed)
 
 

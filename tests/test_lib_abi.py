@@ -62,7 +62,10 @@ def test_product_sources_carry_no_tools_code():
     """The product kernel sources hold only what libmmb.so runs (r06): no
     environment reads and no MMB_DIAG blocks -- the tools build's variants,
     knobs and probes live in tools/diag/ and plug into named MMB_HOOK_*
-    points whose product defaults are compiled here."""
+    points whose product defaults are compiled here.  Nor any build-time
+    switch: the constants once set with -D by clone scripts are constexpr."""
+    macros = ("MMB_SPLIT_TEXT_X", "MMB_SPLIT_TU", "MMB_SPLIT_FU", "NF_UNR", "NF_HU", "NF_ABL",
+              "NF_GA", "NF_GV", "NF_WAVES", "MMB_SQ_PER_WG")
     csrc = os.path.join(ROOT, "multimodal-baselines_amd", "csrc")
     srcs = [f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".cpp"))]
     assert "sif_kernels.hip" in srcs and "pc_kernels.hip" in srcs
@@ -70,6 +73,8 @@ def test_product_sources_carry_no_tools_code():
         text = open(os.path.join(csrc, f)).read()
         assert "getenv" not in text, f
         assert "MMB_DIAG" not in text, f
+        for m in macros:
+            assert m not in text, (f, m)
     # the tails the tools build includes exist; the product's target is empty
     for tail in ("sif_tail.inc", "pc_tail.inc", "mm2_tail.inc", "diag_hooks.h"):
         assert os.path.exists(os.path.join(ROOT, "tools", "diag", tail)), tail
@@ -120,6 +125,10 @@ def test_environment_cannot_redirect_the_product_library(tmp_path):
                          check=True).stdout.strip().splitlines()[-1]
     assert out == os.path.join(ROOT, "multimodal-baselines_amd", "libmmb.so")
     src = open(os.path.join(ROOT, "multimodal-baselines_amd", "mmb_lib.py")).read()
+    assert "os.environ" not in src and "getenv" not in src
+    # nor does the step read options from the environment: its constructor
+    # arguments are the only way to force a path
+    src = open(os.path.join(ROOT, "multimodal-baselines_amd", "pipeline.py")).read()
     assert "os.environ" not in src and "getenv" not in src
 
 

@@ -120,14 +120,13 @@ bool diag_stream_small(const A& a, int grid, hipStream_t stream) {
 // attribute and launch
 template <int I>
 void diag_nf_teams_attr() {
-  if (kNFWaves == 8)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&utt_narrow_fused_kernel<NF_UNR, NF_HU, NF_GA, NF_GV, kNFWaves == 8>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kNFLds));
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kNFLds));
 }
 template <class F>
 bool diag_nf_teams_launch(int teams, const F& f, int64_t grid, hipStream_t stream) {
   if (!teams) return false;
-  utt_narrow_fused_kernel<NF_UNR, NF_HU, NF_GA, NF_GV, kNFWaves == 8><<<static_cast<unsigned>(grid), kNFThreads, kNFLds, stream>>>(f);
+  utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV, true><<<static_cast<unsigned>(grid), kNFThreads, kNFLds, stream>>>(f);
   return true;
 }
 

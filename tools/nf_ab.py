@@ -3,9 +3,9 @@
 on the MOSI bench workload (1M utterances, T 20, A 76, Vd 48, V 3016): the
 kernel's mean launch time over --steps FusedStep runs, the step time, and the
 a2 rows against the two-kernel step's (row-relative).  One library per
-process (tools/ab_libs/build_nf.sh builds the knob variants):
+process:
 
-    python tools/nf_ab.py --lib tools/ab_libs/libmmb_nf_4_1.so
+    python tools/nf_ab.py --lib multimodal-baselines_amd/libmmb.so
 """
 import argparse
 import os
@@ -27,17 +27,6 @@ def main():
     ap.add_argument("--workload", choices=["mosi", "synthetic"], default="mosi",
                     help="synthetic: the headline configs[3] step (T 40, 3 x 300-d, V 400k)")
     args = ap.parse_args()
-    # the launched instantiation must be in the library's code object: HIP
-    # aborts the process otherwise (r05: libmmb_nf_w12_2_1_4_2.so)
-    import re
-    sys.path.insert(0, os.path.join(ROOT, "tools", "ab_libs"))
-    import symcheck
-    name = os.path.basename(args.lib)
-    m = re.match(r"libmmb_nf_w(\d+)_(\d+)_(\d+)_(\d+)_(\d+)", name)
-    want = (symcheck.narrow_symbol(*map(int, m.groups()[1:])) if m else None)
-    if want and want not in symcheck.device_symbols(os.path.abspath(args.lib)):
-        print(f"{name}: {want} not in its gfx950 code object; not loaded", flush=True)
-        return 2
     mmb_lib.load(os.path.abspath(args.lib))
     import torch
     import models
@@ -64,7 +53,7 @@ def main():
     ms = (time.perf_counter() - t0) * 1e3 / args.steps
     try:
         step.check()
-    except Exception as e:  # timing-only ablations (NF_ABL) compute no valid step
+    except Exception as e:  # a timing-only tools build computes no valid step
         print(f"# {os.path.basename(args.lib)} check: {type(e).__name__}", flush=True)
     kn = "mm2_stream_project_narrow" if args.workload == "mosi" else "mm2_stream_project"
     kms = sum(a.elapsed_time(b) for tr in traces for a, b in tr.get(kn, ())) / args.steps
