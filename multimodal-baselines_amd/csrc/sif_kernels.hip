@@ -1674,7 +1674,10 @@ __device__ __forceinline__ void frame_piece(const float* base, int W, int L, int
   } while (0)
 #endif
 
-template <int UNR, bool NT, int DIAG = 0, int PIPE = 0, int SL = kGSlots>
+// TM (the pipelined streamers): bit m set = piece m's rows are wider than 256
+// columns and carry a tail load and tail sums (fused_tail_mask); a set bit on
+// a narrower piece only costs redundant loads, the results are the same.
+template <int UNR, bool NT, int DIAG = 0, int PIPE = 0, int SL = kGSlots, int TM = 7>
 __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void utt_fused_kernel(
     FusedArgs f) {
   const StreamArgs& a = f.s;
@@ -1750,6 +1753,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
     const int wdt[3] = {a.D, a.A, a.Vd};
     float4 cmx[2];
     cmx[0] = cmx[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+    float cmt = 0.f;  // the pipelined streamers' bound of column 256 + lane (in place of cmx[1])
     // Row q (utterance i) of batch j, modality m summed: its power-of-2 scale,
     // the text row's x / aux / column bounds, then the scaled fp16 hi | lo
     // sums into the ring slot (once the slot's previous piece-row was read by
@@ -1759,22 +1763,42 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
     // stay in flight (its x / aux stores are drained once per batch, before
     // the audio piece's first increment -- the projectors read x only after
     // the visual piece).
-    auto finish_row = [&](auto drain_c, int64_t j, int m, int q, int64_t i, const float4 (&num)[2],
-                          const float4 (&sx)[2], const float4 (&sxx)[2], float cnt, float sw) {
+    //
+    // TL, the layout of a row's columns from 256 on (num1 / sx1 / sxx1): 2 =
+    // a second float4 per lane, columns 4 (64 + lane) (the group-at-a-time
+    // streamer), 1 = one float per lane, column 256 + lane (the pipelined
+    // streamers), 0 = the piece has no such columns (W <= 256; the arguments
+    // are unused).  Lanes past the row's end hold a clamped duplicate in
+    // either layout: the row maximum is the same, and nothing of them is
+    // stored.  The ring positions written are the same in all three.
+    auto finish_row = [&](auto drain_c, auto tl_c, int64_t j, int m, int q, int64_t i, const float4& num0,
+                          const float4& sx0, const float4& sxx0, auto num1, auto sx1, auto sxx1,
+                          float cnt, float sw) {
+      constexpr int TL = decltype(tl_c)::value;
       const int W = wdt[m], U = W >> 2;
       const int p = 3 * static_cast<int>(j) + m;  // piece sequence number
-      float mx = 0.f;
-#pragma unroll
-      for (int c = 0; c < 2; ++c) mx = fmaxf(mx, fmaxf(amax4(sx[c]), amax4(sxx[c])));
+      float mx = fmaxf(0.f, fmaxf(amax4(sx0), amax4(sxx0)));
+      if constexpr (TL == 2) mx = fmaxf(mx, fmaxf(amax4(sx1), amax4(sxx1)));
+      if constexpr (TL == 1) mx = fmaxf(mx, fmaxf(fabsf(sx1), fabsf(sxx1)));
       const float rs = row_scale(wave_max_dpp_f32(mx));
       if (m == 0) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const int uu = lane + kWave * c;
-          if (uu < U) {
-            const float4 xr = div4(num[c], cnt);
-            st4(a.num_out + i * D + 4 * uu, xr);  // x = the a2 row
-            cmx[c] = bmax4(cmx[c], xr);
+        if (lane < U) {
+          const float4 xr = div4(num0, cnt);
+          st4(a.num_out + i * D + 4 * lane, xr);  // x = the a2 row
+          cmx[0] = bmax4(cmx[0], xr);
+        }
+        if constexpr (TL == 2) {
+          if (lane + kWave < U) {
+            const float4 xr = div4(num1, cnt);
+            st4(a.num_out + i * D + 4 * (lane + kWave), xr);
+            cmx[1] = bmax4(cmx[1], xr);
+          }
+        }
+        if constexpr (TL == 1) {
+          if (4 * kWave + lane < W) {
+            const float xr = num1 / cnt;
+            a.num_out[i * D + 4 * kWave + lane] = xr;
+            cmt = bmax(cmt, fabsf(xr));
           }
         }
         if (lane == 0) {
@@ -1805,12 +1829,28 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
         *reinterpret_cast<h4*>(srow + o) = h;
         *reinterpret_cast<h4*>(srow + kGPlane + o) = l;
       };
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const int uu = lane + kWave * c;
-        if (uu < U) {
-          put(4 * uu, sx[c]);
-          put(W + 4 * uu, sxx[c]);
+      // one column's hi and lo halves, at the position put() gives it
+      auto put1 = [&](int k, float v) {
+        const float x = v * rs;
+        const _Float16 h = static_cast<_Float16>(x);
+        const int o = (((k >> 3) ^ qx) << 3) + (k & 7);
+        srow[o] = h;
+        srow[kGPlane + o] = static_cast<_Float16>(x - static_cast<float>(h));
+      };
+      if (lane < U) {
+        put(4 * lane, sx0);
+        put(W + 4 * lane, sxx0);
+      }
+      if constexpr (TL == 2) {
+        if (lane + kWave < U) {
+          put(4 * (lane + kWave), sx1);
+          put(W + 4 * (lane + kWave), sxx1);
+        }
+      }
+      if constexpr (TL == 1) {
+        if (4 * kWave + lane < W) {
+          put1(4 * kWave + lane, sx1);
+          put1(W + 4 * kWave + lane, sxx1);
         }
       }
       for (int k = 2 * W + 4 * lane; k < f.kq[m]; k += 4 * kWave) put(k, make_float4(0.f, 0.f, 0.f, 0.f));
@@ -1846,7 +1886,8 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
               const float* base = m == 1 ? a.audio + i * a.L * a.A : a.visual + i * a.L * a.Vd;
               frame_piece<UNR, NT>(base, W, a.L, lane, sx, sxx);
             }
-            finish_row(std::true_type{}, j, m, q, i, num, sx, sxx, cnt, sw);
+            finish_row(std::true_type{}, std::integral_constant<int, 2>{}, j, m, q, i, num[0], sx[0], sxx[0],
+                       num[1], sx[1], sxx[1], cnt, sw);
           }
         }
       }
@@ -1854,7 +1895,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
       // Pipelined streamer: the (row, frame group) sequence of one (batch,
       // modality) piece -- this wave's rows i0 + 4 r, ceil(L / UNR) groups of
       // UNR frames each -- as ONE load pipeline two groups deep: group g + 1's
-      // 2 UNR loads are issued before group g is summed (alternating register
+      // UNR or 2 UNR loads are issued before group g is summed (alternating register
       // sets b0 / b1; the compiler's counted vmcnt waits only for the older
       // group), so loads stay in flight across group and row boundaries where
       // the group-at-a-time streamer drained them.  Text rows: row r + 1's ids
@@ -1900,17 +1941,32 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
           }
         }
       };
-      auto piece = [&](auto text_c, int64_t j, int m, int64_t i0, int nrows) {
-        constexpr bool TEXT = decltype(text_c)::value;
+      // A frame group in flight: per frame one b128 load (lane l: columns 4 l
+      // .. 4 l + 3) and, where the piece is wider than 256 columns (TM bit m),
+      // one b32 load of column 256 + l -- 5 VGPRs per frame where two b128
+      // loads took 8, 3 of them dead on the 300-wide rows' 53 clamped lanes.
+      // Widths are <= 320 (mmb_mm2_stream_project_supported): 64 tail lanes
+      // suffice.  Both loads clamp their column to the row's last (no exec
+      // masking: the masked second load measured slower, below), share the
+      // descriptor, the scalar row offset and the cache policy.
+      struct Grp {
+        float4 a[UNR];
+        float b[UNR];
+      };
+      static_assert(4 * UNR + 8 < 64, "two groups of two loads per frame and a row's stores fit vmcnt's 6 bits");
+      auto piece = [&](auto m_c, int64_t j, int64_t i0, int nrows) {
+        constexpr int m = decltype(m_c)::value;
+        constexpr bool TEXT = m == 0;
+        constexpr bool TAIL = ((TM >> m) & 1) != 0;
         const int W = wdt[m], UW = W >> 2;
-        const int c0 = 4 * min(lane, UW - 1), c1 = 4 * min(lane + kWave, UW - 1);
         const int ngr = (L + UNR - 1) / UNR, ng = nrows * ngr;
         const float* src = TEXT ? (gather ? a.table : a.text_dense) : (m == 1 ? a.audio : a.visual);
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
         int cur = 0;                        // the row being summed
         int rid_c = -1, rid_n = -1, raw_n = -1;
         float w_c = 0.f, w_n = 0.f, wd_n = 0.f;
-        float4 num[2], sx[2], sxx[2];
+        float4 num, sx, sxx;
+        float numt = 0.f, sxt = 0.f, sxxt = 0.f;  // column 256 + lane
         float cnt = 0.f, sw = 0.f;
         if constexpr (TEXT) {
           int raw;
@@ -1924,8 +1980,8 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
         // issued on its 11 live lanes only, the others zeroed, measured 23.37
         // vs 22.24 ms: the divergent branch costs more than the clamped
         // duplicate addresses, which the L1 coalesces.)
-        const int vo0 = 4 * c0, vo1 = 4 * c1;
-        auto issue = [&](int g, float4 (&v)[UNR][2]) {
+        const int vo0 = 16 * min(lane, UW - 1), vo1 = 4 * min(4 * kWave + lane, W - 1);
+        auto issue = [&](int g, Grp& v) {
           const int rr = g / ngr, t0 = (g - rr * ngr) * UNR;
           const int64_t i = i0 + 4 * rr;
           int rid = 0;
@@ -1945,35 +2001,40 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
               so = t * W * 4;
             }
             constexpr int pol = (!TEXT && NT) ? 2 : 0;  // non-temporal frame streams
-            v[u][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo0, so, pol));
-            v[u][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo1, so, pol));
+            v.a[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo0, so, pol));
+            if constexpr (TAIL)
+              v.b[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, vo1, so, pol));
           }
         };
-        auto sum_frame = [&](int t, const float4 (&v)[2]) {
+        auto sum_frame = [&](int t, const float4& va, float vb) {
           if constexpr (TEXT) {
             const int r = __builtin_amdgcn_readlane(rid_c, t);
             const float wt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w_c), t));
             const bool ok = r >= 0;  // an out-of-range id (flagged) contributes a zero row
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-              const float4 x = ok ? v[c] : z4;
-              fma4(num[c], wt, x);
-              add4(sx[c], x);
-              sq4(sxx[c], x);
+            const float4 x = ok ? va : z4;
+            fma4(num, wt, x);
+            add4(sx, x);
+            sq4(sxx, x);
+            if constexpr (TAIL) {
+              const float xt = ok ? vb : 0.f;
+              numt = fmaf(wt, xt, numt);
+              sxt += xt;
+              sxxt = fmaf(xt, xt, sxxt);
             }
           } else {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-              add4(sx[c], v[c]);
-              sq4(sxx[c], v[c]);
+            add4(sx, va);
+            sq4(sxx, va);
+            if constexpr (TAIL) {
+              sxt += vb;
+              sxxt = fmaf(vb, vb, sxxt);
             }
           }
         };
-        auto consume = [&](int g, const float4 (&v)[UNR][2]) {
+        auto consume = [&](int g, const Grp& v) {
           const int rr = g / ngr, gg = g - rr * ngr, t0 = gg * UNR;
           if (gg == 0) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) num[c] = sx[c] = sxx[c] = z4;
+            num = sx = sxx = z4;
+            numt = sxt = sxxt = 0.f;
             if constexpr (TEXT) {
               cnt = static_cast<float>(__builtin_popcountll(__builtin_amdgcn_ballot_w64(w_c != 0.f)));
               sw = wave_sum_dpp_f32(w_c);
@@ -1988,15 +2049,16 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
           }
           if (t0 + UNR <= L) {
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) sum_frame(t0 + u, v[u]);
+            for (int u = 0; u < UNR; ++u) sum_frame(t0 + u, v.a[u], TAIL ? v.b[u] : 0.f);
           } else {
 #pragma unroll
             for (int u = 0; u < UNR; ++u)
-              if (t0 + u < L) sum_frame(t0 + u, v[u]);
+              if (t0 + u < L) sum_frame(t0 + u, v.a[u], TAIL ? v.b[u] : 0.f);
           }
           if (gg == ngr - 1) {
             const int q = uw + 4 * rr;
-            finish_row(std::false_type{}, j, m, q, i0 + 4 * rr, num, sx, sxx, cnt, sw);
+            finish_row(std::false_type{}, std::integral_constant<int, TAIL ? 1 : 0>{}, j, m, q, i0 + 4 * rr, num,
+                       sx, sxx, numt, sxt, sxxt, cnt, sw);
             cur = rr + 1;
             if constexpr (TEXT) {
               rid_c = rid_n;
@@ -2004,7 +2066,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
             }
           }
         };
-        float4 b0[UNR][2], b1[UNR][2];
+        Grp b0, b1;
         issue(0, b0);
         int g = 0;
 #pragma unroll 1
@@ -2028,13 +2090,14 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
       // flight across piece and batch boundaries too; the next batch's first
       // text row is staged during the visual piece's last groups.  Pieces with
       // an odd group count drain as before.
-      float4 pb0[UNR][2], pb1[UNR][2];
+      Grp pb0, pb1;
       bool pre = false;  // pb0 holds this piece's group 0 (issued by the previous piece)
       int rid_pre = -1, raw_p = -1;
       float w_pre = 0.f, wd_p = 0.f;
       auto piece2 = [&](auto m_c, int64_t j, int64_t i0, int nrows, int64_t ni0, int nnr) {
         constexpr int M = decltype(m_c)::value;
         constexpr bool TEXT = M == 0;
+        constexpr bool TAIL = ((TM >> M) & 1) != 0;
         const int W = wdt[M], UW = W >> 2;
         const int ngr = (L + UNR - 1) / UNR, ng = nrows * ngr;
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -2042,9 +2105,10 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
         if constexpr (M == 2) {
           // the text piece's x / aux stores complete before any visual
           // increment (the projectors read x after the visual piece): with
-          // group 0 in flight the 16 newest operations are its loads
+          // group 0 in flight the newest operations are its loads, one or
+          // two per frame
           if (pre) {
-            asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(UNR * (TAIL ? 2 : 1)) : "memory");
           } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           }
@@ -2052,7 +2116,8 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
         int cur = 0;
         int rid_c = -1, rid_n = -1, raw_n = -1;
         float w_c = 0.f, w_n = 0.f, wd_n = 0.f;
-        float4 num[2], sx[2], sxx[2];
+        float4 num, sx, sxx;
+        float numt = 0.f, sxt = 0.f, sxxt = 0.f;  // column 256 + lane
         float cnt = 0.f, sw = 0.f;
         if constexpr (TEXT) {
           if (pre) {
@@ -2065,17 +2130,18 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
             tok_resolve(raw, wd, rid_c, w_c);
           }
         }
-        const int vo0 = 16 * min(lane, UW - 1), vo1 = 16 * min(lane + kWave, UW - 1);
+        const int vo0 = 16 * min(lane, UW - 1), vo1 = 4 * min(4 * kWave + lane, W - 1);
         // group g of this piece (or, NX, group 0 of the next piece) into v
-        auto load_group = [&](auto nx_c, int g, float4 (&v)[UNR][2]) {
+        auto load_group = [&](auto nx_c, int g, Grp& v) {
           constexpr bool NX = decltype(nx_c)::value;
           constexpr int MM = NX ? (M + 1) % 3 : M;
           constexpr bool T2 = MM == 0;
+          constexpr bool TAIL2 = ((TM >> MM) & 1) != 0;
           const int rr = NX ? 0 : g / ngr, t0 = NX ? 0 : (g - rr * ngr) * UNR;
           const int64_t i = NX ? (M == 2 ? ni0 : i0) : i0 + 4 * rr;
           const int W2 = wdt[MM], U2 = W2 >> 2;
           const float* s2 = T2 ? (gather ? a.table : a.text_dense) : (MM == 1 ? a.audio : a.visual);
-          const int o0 = NX ? 16 * min(lane, U2 - 1) : vo0, o1 = NX ? 16 * min(lane + kWave, U2 - 1) : vo1;
+          const int o0 = NX ? 16 * min(lane, U2 - 1) : vo0, o1 = NX ? 4 * min(4 * kWave + lane, W2 - 1) : vo1;
           int rid = 0;
           if constexpr (T2) rid = NX ? rid_pre : (rr == cur ? rid_c : rid_n);
           const bool rowbase = !T2 || !gather;
@@ -2093,36 +2159,41 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
               so = t * W2 * 4;
             }
             constexpr int pol = (!T2 && NT) ? 2 : 0;  // non-temporal frame streams
-            v[u][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o0, so, pol));
-            v[u][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o1, so, pol));
+            v.a[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o0, so, pol));
+            if constexpr (TAIL2)
+              v.b[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, o1, so, pol));
           }
         };
-        auto issue = [&](int g, float4 (&v)[UNR][2]) { load_group(std::false_type{}, g, v); };
-        auto sum_frame = [&](int t, const float4 (&v)[2]) {
+        auto issue = [&](int g, Grp& v) { load_group(std::false_type{}, g, v); };
+        auto sum_frame = [&](int t, const float4& va, float vb) {
           if constexpr (TEXT) {
             const int r = __builtin_amdgcn_readlane(rid_c, t);
             const float wt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w_c), t));
             const bool ok = r >= 0;  // an out-of-range id (flagged) contributes a zero row
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-              const float4 x = ok ? v[c] : z4;
-              fma4(num[c], wt, x);
-              add4(sx[c], x);
-              sq4(sxx[c], x);
+            const float4 x = ok ? va : z4;
+            fma4(num, wt, x);
+            add4(sx, x);
+            sq4(sxx, x);
+            if constexpr (TAIL) {
+              const float xt = ok ? vb : 0.f;
+              numt = fmaf(wt, xt, numt);
+              sxt += xt;
+              sxxt = fmaf(xt, xt, sxxt);
             }
           } else {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-              add4(sx[c], v[c]);
-              sq4(sxx[c], v[c]);
+            add4(sx, va);
+            sq4(sxx, va);
+            if constexpr (TAIL) {
+              sxt += vb;
+              sxxt = fmaf(vb, vb, sxxt);
             }
           }
         };
-        auto consume = [&](int g, const float4 (&v)[UNR][2]) {
+        auto consume = [&](int g, const Grp& v) {
           const int rr = g / ngr, gg = g - rr * ngr, t0 = gg * UNR;
           if (gg == 0) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) num[c] = sx[c] = sxx[c] = z4;
+            num = sx = sxx = z4;
+            numt = sxt = sxxt = 0.f;
             if constexpr (TEXT) {
               cnt = static_cast<float>(__builtin_popcountll(__builtin_amdgcn_ballot_w64(w_c != 0.f)));
               sw = wave_sum_dpp_f32(w_c);
@@ -2141,15 +2212,16 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
           }
           if (t0 + UNR <= L) {
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) sum_frame(t0 + u, v[u]);
+            for (int u = 0; u < UNR; ++u) sum_frame(t0 + u, v.a[u], TAIL ? v.b[u] : 0.f);
           } else {
 #pragma unroll
             for (int u = 0; u < UNR; ++u)
-              if (t0 + u < L) sum_frame(t0 + u, v[u]);
+              if (t0 + u < L) sum_frame(t0 + u, v.a[u], TAIL ? v.b[u] : 0.f);
           }
           if (gg == ngr - 1) {
             const int q = uw + 4 * rr;
-            finish_row(std::false_type{}, j, M, q, i0 + 4 * rr, num, sx, sxx, cnt, sw);
+            finish_row(std::false_type{}, std::integral_constant<int, TAIL ? 1 : 0>{}, j, M, q, i0 + 4 * rr, num,
+                       sx, sxx, numt, sxt, sxxt, cnt, sw);
             cur = rr + 1;
             if constexpr (TEXT) {
               rid_c = rid_n;
@@ -2254,19 +2326,20 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
           const int64_t i0 = row0 + uw;
           const int nrows = i0 < rend ? static_cast<int>(min<int64_t>(kGR / 4, (rend - i0 + 3) / 4)) : 0;
           if (nrows == 0) continue;
-          piece(std::true_type{}, j, 0, i0, nrows);
+          piece(std::integral_constant<int, 0>{}, j, i0, nrows);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // x / aux stores before the audio increments
-          piece(std::false_type{}, j, 1, i0, nrows);
-          piece(std::false_type{}, j, 2, i0, nrows);
+          piece(std::integral_constant<int, 1>{}, j, i0, nrows);
+          piece(std::integral_constant<int, 2>{}, j, i0, nrows);
         }
       }
     }
     if (a.cmax_part) {  // this wave's column bounds (mmb_gram_i8)
       const int64_t wid = static_cast<int64_t>(blockIdx.x) * 4 + wave;
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const int uu = lane + kWave * c;
-        if (uu < (D >> 2)) st4(a.cmax_part + wid * D + 4 * uu, cmx[c]);
+      if (lane < (D >> 2)) st4(a.cmax_part + wid * D + 4 * lane, cmx[0]);
+      if constexpr (PIPE == 0) {
+        if (lane + kWave < (D >> 2)) st4(a.cmax_part + wid * D + 4 * (lane + kWave), cmx[1]);
+      } else {
+        if (4 * kWave + lane < D) a.cmax_part[wid * D + 4 * kWave + lane] = cmt;
       }
     }
     FUSED_PROBE(1 + wave);
@@ -2483,26 +2556,54 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
   FUSED_PROBE(1 + wave);
 }
 
-template <int DIAG, int UNR = 8, int PIPE = 0, int SL = kGSlots>
+template <int DIAG, int UNR = 8, int PIPE = 0, int SL = kGSlots, int TM = 7>
 static void launch_fused_v(const FusedArgs& f, int grid, hipStream_t stream) {
   constexpr size_t lds = fused_lds_bytes(SL);
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&utt_fused_kernel<UNR, true, DIAG, PIPE, SL>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&utt_fused_kernel<UNR, true, DIAG, PIPE, SL, TM>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     attr = true;
   }
-  utt_fused_kernel<UNR, true, DIAG, PIPE, SL><<<grid, kFThreads, lds, stream>>>(f);
+  utt_fused_kernel<UNR, true, DIAG, PIPE, SL, TM><<<grid, kFThreads, lds, stream>>>(f);
 }
+// the pipelined streamer specialised for the pieces that carry a row tail
+// (a piece-level, wave-uniform choice made here, once per launch)
+static int fused_tail_mask(const FusedArgs& f) {
+  return (f.s.D > 4 * kWave ? 1 : 0) | (f.s.A > 4 * kWave ? 2 : 0) | (f.s.Vd > 4 * kWave ? 4 : 0);
+}
+template <int UNR, int PIPE>
+static void launch_fused_tm(const FusedArgs& f, int grid, hipStream_t stream) {
+  switch (fused_tail_mask(f)) {
+    case 0: launch_fused_v<0, UNR, PIPE, kGSlots, 0>(f, grid, stream); break;
+    case 1: launch_fused_v<0, UNR, PIPE, kGSlots, 1>(f, grid, stream); break;
+    case 2: launch_fused_v<0, UNR, PIPE, kGSlots, 2>(f, grid, stream); break;
+    case 3: launch_fused_v<0, UNR, PIPE, kGSlots, 3>(f, grid, stream); break;
+    case 4: launch_fused_v<0, UNR, PIPE, kGSlots, 4>(f, grid, stream); break;
+    case 5: launch_fused_v<0, UNR, PIPE, kGSlots, 5>(f, grid, stream); break;
+    case 6: launch_fused_v<0, UNR, PIPE, kGSlots, 6>(f, grid, stream); break;
+    default: launch_fused_v<0, UNR, PIPE, kGSlots, 7>(f, grid, stream); break;
+  }
+}
+// the pipelined streamer's frames per load group (two groups in flight per
+// wave: 20 frames, 100 VGPRs of buffers).  Same-process sweep at 1M rows, T =
+// 40 (four whole groups per row), fused kernel ms: 8 frames 21.3, 10 frames
+// 20.9, 12 frames 22.0 (its last group of a row is one third live); the
+// parent's float4 tails with 8 frames 22.1.  The other
+// candidates live in the tools build (MMB_FUSED_UNR).
+constexpr int kFUnr = 10;
 // streamer: 1 = pipelined (two groups in flight: kernel 23.35 -> 22.49 ms,
 // step 25.14 -> 24.41 ms in a same-process A/B, r02k); 2 (default) = also
 // prefetching across piece and batch boundaries (22.32 -> 22.14 ms, r02y);
-// 0 = one group at a time (the fallback for rows of < 3 frame groups or a
-// word table >= 2 GB, and the bit-identical reference of the tests)
+// 0 = one group at a time, 8 frames each, float4 row tails (the fallback for
+// rows of < 3 frame groups or a word table >= 2 GB, and the bit-identical
+// reference of the tests)
 static bool fused_pipe_ok(const FusedArgs& f, int un) {
   // the pipelined streamer stages a text row's tokens two groups before its
-  // first group is issued: >= 3 groups per row; it addresses the word table
-  // through one buffer descriptor (< 2^31 bytes)
+  // first group is issued (ids at the row before's first group, wtab[id] at
+  // its second): >= 3 groups of un frames per row -- T >= 21 at the product's
+  // 10-frame groups, shorter rows take the fallback; it addresses the word
+  // table through one buffer descriptor (< 2^31 bytes)
   return (f.s.L + un - 1) / un >= 3 && (f.s.ids == nullptr || f.s.V * f.s.D * 4 < (int64_t{1} << 31));
 }
 
@@ -2517,8 +2618,8 @@ static int launch_fused(const FusedArgs& f, hipStream_t stream, int* parts) {
 #define MMB_HOOK_FUSED_LAUNCH false
 #endif
   if (!(MMB_HOOK_FUSED_LAUNCH)) {
-    if (fused_pipe_ok(f, 8)) {
-      launch_fused_v<0, 8, 2>(f, grid, stream);
+    if (fused_pipe_ok(f, kFUnr)) {
+      launch_fused_tm<kFUnr, 2>(f, grid, stream);
     } else {
       launch_fused_v<0, 8, 0>(f, grid, stream);
     }

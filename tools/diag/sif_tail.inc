@@ -48,23 +48,37 @@ bool diag_wave_launch(const A& a, int grid, hipStream_t stream) {
 // ablations, MMB_FUSED_PIPE streamer pipelining, MMB_FUSED_SLOTS ring slots
 template <class F>
 bool diag_fused_launch(const F& f, int grid, hipStream_t stream) {
-  auto fused_unr = [] { return diag_knob("MMB_FUSED_UNR", 8); };
   auto fused_diag = [] { return diag_knob("MMB_FUSED_DIAG", 0); };
   auto fused_pipe = [] { return diag_knob("MMB_FUSED_PIPE", 2); };
   auto fused_slots = [] { return diag_knob("MMB_FUSED_SLOTS", kGSlots); };
-  const int dg = fused_diag(), un = fused_unr();
+  const int dg = fused_diag();
+  // the product's streamer (PIPE 2, two groups of kFUnr frames in flight)
+  // and its ablations; everything else defaults to 8-frame groups
+  const bool prod = fused_pipe() == 2 && (dg == 0 || dg == 1 || dg == 4 || dg == 128 || dg == 256);
+  const int un = diag_knob("MMB_FUSED_UNR", prod ? kFUnr : 8);
   const bool pipe = fused_pipe() != 0 && fused_pipe_ok(f, un);
-  if (pipe && un == 8 && fused_pipe() == 2 && (dg == 0 || dg == 1 || dg == 4 || dg == 128 || dg == 256)) {
+  if (pipe && prod && un == kFUnr) {
     if (dg == 1) {
-      launch_fused_v<1, 8, 2>(f, grid, stream);
+      launch_fused_v<1, kFUnr, 2>(f, grid, stream);
     } else if (dg == 4) {
-      launch_fused_v<4, 8, 2>(f, grid, stream);
+      launch_fused_v<4, kFUnr, 2>(f, grid, stream);
     } else if (dg == 128) {
-      launch_fused_v<128, 8, 2>(f, grid, stream);
+      launch_fused_v<128, kFUnr, 2>(f, grid, stream);
     } else if (dg == 256) {
-      launch_fused_v<256, 8, 2>(f, grid, stream);
+      launch_fused_v<256, kFUnr, 2>(f, grid, stream);
     } else {
+      launch_fused_tm<kFUnr, 2>(f, grid, stream);
+    }
+  } else if (pipe && prod && dg == 0 && (un == 8 || un == 10 || un == 12)) {
+    // the pipeline-depth candidates: two groups of MMB_FUSED_UNR frames in
+    // flight (16, 20 or 24 frames); every piece with its tail load, which
+    // is right at any width
+    if (un == 8) {
       launch_fused_v<0, 8, 2>(f, grid, stream);
+    } else if (un == 10) {
+      launch_fused_v<0, 10, 2>(f, grid, stream);
+    } else {
+      launch_fused_v<0, 12, 2>(f, grid, stream);
     }
   } else if (pipe && un == 8) {
     switch (dg) {
