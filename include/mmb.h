@@ -116,12 +116,15 @@ int mmb_xt_omega(const float* num, const float* cnt, int64_t n, int d, const dou
  * subspace the reference's iterations build, and the final SVD of Q^T X is
  * solved as a k x k (generalised) symmetric eigenproblem.  One workgroup, fp64.
  *   transposed = (n_total < d): z0 = X^T Omega_n, else z0 = Omega_d [d,k].
- * pc_out [npc, d] float64.  d <= 512, k <= 16.
+ * pc_out [npc, d] float64.  d <= 512, k <= min(16, d): a block wider than the
+ * space has singular k x k factors and is rejected (MMB_EINVAL, as in the two
+ * entry points below); its first d columns already span everything.
  * replaces: sif_functions.compute_pc /root/reference/sif_functions.py:58-67 */
 int mmb_pc_solve(const double* g, int d, const double* z0, int k, int npc, int n_iter,
                  int transposed, double* pc_out, hipStream_t stream);
 
-/* The same solve on ceil(d/16) workgroups (d <= 320, k <= 16): each keeps
+/* The same solve on ceil(d/16) workgroups (d <= 320, k <= min(16, d): a wider
+ * block is rejected, MMB_EINVAL): each keeps
  * 16 rows of G in registers, the tiles of every power-iteration product are
  * exchanged in-launch (write-through stores + an arrival counter), and every
  * workgroup runs the identical CholeskyQR; workgroup 0 runs the final
@@ -135,6 +138,9 @@ int mmb_pc_solve(const double* g, int d, const double* z0, int k, int npc, int n
  * arrival count outside the round's range); pc_out is then NaN and ws must
  * be re-zeroed before the next call.
  * replaces: sif_functions.compute_pc /root/reference/sif_functions.py:58-67 */
+int mmb_pc_solve_mc(const double* g, int d, const double* z0, int k, int npc, int n_iter,
+                    int transposed, double* pc_out, void* ws, int32_t* flag, hipStream_t stream);
+
 /* The step's status word in one launch: out[0] = flag[0] | (nonfinite_bit if
  * any of the n values of pc is not finite), flag nullable (0).  What a
  * checked step (pipeline.FusedStep.status) reads back with one sync; the
@@ -157,13 +163,12 @@ size_t mmb_pc_solve_mc_ws_bytes(int d);
  * launch into ws (which holds both; mmb_pc_solve_mc_ws_bytes), then the
  * solve -- where mmb_xt_omega + mmb_pc_solve_mc took two launches before
  * it.  The same z0 (the same per-lane sums) and PC.
+ * n < d <= 320, n <= 320, k <= min(16, d) (a wider block: MMB_EINVAL).
  * replaces: sif_functions.compute_pc for a split of n < d rows
  *   /root/reference/sif_functions.py:58-67 (sklearn extmath.py:562-566)    */
 int mmb_pc_solve_mc_xt(const double* g, int d, const float* x, int64_t n, const double* omega,
                        int k, int npc, int n_iter, double* pc_out, void* ws, int32_t* flag,
                        hipStream_t stream);
-int mmb_pc_solve_mc(const double* g, int d, const double* z0, int k, int npc, int n_iter,
-                    int transposed, double* pc_out, void* ws, int32_t* flag, hipStream_t stream);
 
 /* ---------------------------------------------------------------- a4
  * out[i] = x_i - sum_c (x_i . pc_c) pc_c   in float64, x_i = num[i]/cnt[i]

@@ -2433,9 +2433,19 @@ __global__ __launch_bounds__(kPnNT) void pc_solve_mc_kernel(const double* __rest
         for (int reg = 0; reg < 4; ++reg) sY[(tt * 16 + (lane >> 4) + 4 * reg) * kP16W + (lane & 15)] = acc[reg];
       }
       __syncthreads();
-      double* zb = part;  // Z into sZ's place, the H tiles' block becomes the scratch
-      part = sZ;
-      sZ = zb;
+      if (Dp * kP16W >= 2 * kPnNW * 256) {
+        double* zb = part;  // Z into sZ's place, the H tiles' block becomes the scratch
+        part = sZ;
+        sZ = zb;
+      } else {
+        // Dp < 256: the H tiles' block ([Dp][16]) is smaller than the scratch
+        // the two Grams below need (2 x 8 waves x 256 partials), and G Z lies
+        // right behind it -- as the scratch it let those partials overwrite
+        // G Z's first rows (a wrong PC at every d <= 240 of the direct
+        // branch).  Copy Z over H instead; `part` keeps its own block.
+        for (int e = tid; e < Dp * kP16W; e += kPnNT) sZ[e] = part[e];
+        __syncthreads();
+      }
       PC_MARK(45 + 2 * n_iter);
     } else {
       // the explicit block's exchange follows: no workgroup may arrive at
@@ -3176,6 +3186,16 @@ extern "C" int mmb_pc_solve(const double* g, int d, const double* z0, int k, int
                             int transposed, double* pc_out, hipStream_t stream) {
   MMB_REQUIRE(g && z0 && pc_out && d > 1 && d <= kMaxD && k >= 1 && k <= kMaxK);
   MMB_REQUIRE(npc >= 1 && npc <= k && n_iter >= 0);
+  // a block wider than the space: no k > d columns of R^d are orthonormal.
+  // A rank-deficient block with k <= d is fine -- MGS^2 normalises the
+  // columns past the rank into the complement of G's range, where they add
+  // nothing -- but with k > d there is no complement: they land back inside
+  // the span, Z^T Z is not the identity, and the tail, which takes Z as
+  // orthonormal (the transposed branch's ordinary eigenproblem of Z^T G Z;
+  // the direct branch's Cholesky of a singular W, its failed pivots clamped),
+  // returns a wrong or NaN PC.  The caller narrows the block to d columns,
+  // which already span everything (pipeline.pc_solve)
+  MMB_REQUIRE(k <= d);
   if (d <= kP16MaxD) {
     const size_t lds = p16_lds_bytes(d);
     static bool attr = false;
@@ -3233,7 +3253,7 @@ extern "C" int mmb_pc_solve_mc(const double* g, int d, const double* z0, int k, 
                                int transposed, double* pc_out, void* ws, int32_t* flag,
                                hipStream_t stream) {
   MMB_REQUIRE(g && z0 && pc_out && ws && d > 1 && d <= kP16MaxD && k >= 1 && k <= kP16W);
-  MMB_REQUIRE(npc >= 1 && npc <= k && n_iter >= 0);
+  MMB_REQUIRE(npc >= 1 && npc <= k && n_iter >= 0 && k <= d);  // (k <= d: as mmb_pc_solve)
   MMB_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0);
   return launch_solve_mc(g, d, z0, k, npc, n_iter, transposed, pc_out, ws, flag, false, stream);
 }
@@ -3242,7 +3262,7 @@ extern "C" int mmb_pc_solve_mc_xt(const double* g, int d, const float* x, int64_
                                   const double* omega, int k, int npc, int n_iter, double* pc_out,
                                   void* ws, int32_t* flag, hipStream_t stream) {
   MMB_REQUIRE(g && x && omega && pc_out && ws && d > 1 && d <= kP16MaxD && k >= 1 && k <= kP16W);
-  MMB_REQUIRE(n >= 1 && n < d && n <= kXtMaxN && npc >= 1 && npc <= k && n_iter >= 0);
+  MMB_REQUIRE(n >= 1 && n < d && n <= kXtMaxN && npc >= 1 && npc <= k && n_iter >= 0 && k <= d);
   MMB_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0);
   const int T = (d + 15) / 16;
   double* g2 = reinterpret_cast<double*>(static_cast<char*>(ws) + 16) + static_cast<size_t>(2) * (d / 16 + 1) * 512;

@@ -205,6 +205,12 @@ def pc_solve(G: torch.Tensor, z0: torch.Tensor, npc: int, transposed: bool,
     its own flag (FusedStep, graph-capturable) checks it later; without one,
     this call checks a flag of its own and raises here (one host sync)."""
     d = G.shape[0]
+    if z0.shape[1] > d:
+        # a block wider than the space (d < npc + 10): its first d columns
+        # span the same subspace -- generically all of R^d, or X's whole row
+        # space in the transposed branch -- so the PC is the exact one, as
+        # sklearn's is there; the kernels' k x k factors need k <= d
+        z0 = z0[:, :d].contiguous()
     k = z0.shape[1]
     pc = out if out is not None else torch.empty((npc, d), dtype=torch.float64, device=G.device)
     if d <= PC_SOLVE_MC_MAX_D and k <= 16:
@@ -1043,7 +1049,7 @@ class FusedStep:
         """G (this rank's rows) -> pc: Omega, RCCL all-reduce of G, the solve."""
         d, k = self.d, self.npc + N_OVERSAMPLES
         if (self.n_total < d and self.allreduce is None and self.row0 == 0
-                and self.n_total == self.n and self.solve_ws is not None and k <= 16):
+                and self.n_total == self.n and self.solve_ws is not None and k <= min(16, d)):
             # the transposed branch over all of Omega's rows, unsharded: X^T
             # Omega and the squared matrix in one launch in front of the
             # solve (mmb_pc_solve_mc_xt)

@@ -5,8 +5,15 @@ arithmetic runs on the GPU through libmmb (no CPU fallback):
 
 * seq2weight            -> mmb_seq2weight   (bit-exact, sif_functions.py:8-15)
 * get_weighted_average  -> mmb_sif_wavg     (fp32 rows, f64 result, :28-56)
-* compute_pc            -> mmb_gram + mmb_pc_solve (sklearn TruncatedSVD(npc,
-                           n_iter=7, random_state=0) replayed on the Gram, :58-67)
+* compute_pc            -> mmb_gram + the solve (sklearn TruncatedSVD(npc,
+                           n_iter=7, random_state=0) replayed on the Gram, :58-67):
+                           X of width d <= 320 takes mmb_pc_solve_mc (ceil(d / 16)
+                           workgroups), 320 < d <= 512 the one-workgroup
+                           mmb_pc_solve (pc_solve_kernel; its pc_solve16_kernel
+                           for d <= 320 is the same solve in one workgroup); d > 512
+                           raises MMBError, npc > 6 ValueError.  Where d < npc + 10
+                           the start block is narrowed to its first d columns
+                           (pipeline.pc_solve): they span the same space
 * remove_pc             -> the above + mmb_pc_remove (f64, :69-81)
 * SIF_embedding         -> all of it fused on device, one upload/download (:84-96)
 
