@@ -455,11 +455,15 @@ int mmb_mlp_eval(const float* latents, const float* labels, const int64_t* perm,
  * stalls (~1 s) or finds ws dirty (the parameters are then invalid and ws
  * must be re-zeroed).  The P = ceil(h / 32) workgroups are launched
  * cooperatively (co-resident, or the launch fails) after an occupancy check
- * (MMB_EINVAL when the device cannot hold them at once).  d % 4 == 0, d <= 512, h <= 512,
- * n_out <= 16.
+ * (MMB_EINVAL when the device cannot hold them at once).  h <= 512,
+ * n_out <= 16, batch <= 32, d % 4 == 0 and d <= mmb_mlp_train_max_d(n_out):
+ * 448 for n_out <= 13, 416 for n_out = 14..16 (two mini-batches of rows,
+ * padded to 32 features, share the workgroup's LDS with 129 n_out floats of
+ * outputs; 0 for an n_out outside 1..16).  Anything else: MMB_EINVAL.
  * replaces: sentiment_model.train_sentiment loop incl. its validation passes
  *   /root/reference/sentiment_model.py:76-127                               */
 size_t mmb_mlp_workspace_bytes(int d, int h);
+int mmb_mlp_train_max_d(int n_out);
 int mmb_mlp_train(const float* latents, const float* labels, const int64_t* perm,
                   int64_t n_per_epoch, int n_epochs, int batch, int d, int h, int o, float lr,
                   float* w1, float* b1, float* w2, float* b2, float* step_loss,
@@ -481,7 +485,8 @@ int mmb_word_normalize(const float* table, int64_t v, int d, float* wn, hipStrea
 /* lp[b] = sum_t mask[b,t] log(alpha_b w[b,t] + (1-alpha_b) score_bt / Z_b),
  * Z_b = sum_{v<V} (1 - acos(cos(l_b, table_v))/pi), alpha_b = 1/(a Z_b + 1),
  * score_bt = 1 - acos(cos(l_b, e_bt))/pi, e_bt = table[ids[b,t]] (ids non-null)
- * or sent_dense[b,t,:].  d <= 320 for the MFMA Z kernel.  ws: scratch of
+ * or sent_dense[b,t,:].  d <= 320 (forward and backward; wider: MMB_EINVAL,
+ * nothing launched).  ws: scratch of
  * mmb_word_workspace_bytes(b, d, v).  With want_grad, state [b,4], gsum
  * [b, pad(d)] and cos_out [b, l] are written for mmb_word_logprob_backward.
  * replaces: losses.get_word_log_prob_angular2 /root/reference/losses.py:68-95

@@ -32,6 +32,7 @@ namespace mmb {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr float kPi = 3.14159265358979323846f;
 constexpr float kCosEps = 1e-8f;  // torch cosine_similarity eps
+constexpr int kWordMaxD = 320;    // word_zsum_kernel<NT> is instantiated for NT = pad16(d) / 16 <= 20
 
 __host__ __device__ inline int pad16(int d) { return (d + 15) / 16 * 16; }
 
@@ -236,7 +237,9 @@ __global__ __launch_bounds__(256) void word_finish_kernel(const float* __restric
     eu = wave_sum(eu);
     const float c = eu / fmaxf(sqrtf(ee), kCosEps);
     const float score = 1.f - acosf(c) / kPi;
-    const float P = alpha * w[b * L + t] + (1.f - alpha) * score / Z;
+    // (1 - alpha) / Z = a alpha exactly; 1.f - alpha cancels where a Z is
+    // small (a table of a few words): its rounding is 2^-24 / (a Z) of it
+    const float P = alpha * w[b * L + t] + a * alpha * score;
     if (lane == 0) {
       if (cos_out) cos_out[b * L + t] = c;
       acc += static_cast<double>(logf(P) * mask[b * L + t]);
@@ -267,20 +270,23 @@ __global__ __launch_bounds__(256) void word_backward_kernel(
   __shared__ float s_sc[4][2];   // per-wave A, sum beta c / s
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const int64_t b = blockIdx.x;
-  const float Z = state[b * 4 + 0], alpha = state[b * 4 + 1], h = state[b * 4 + 2];
+  const float alpha = state[b * 4 + 1], h = state[b * 4 + 2];
   const float nc = fmaxf(state[b * 4 + 3], kCosEps);
   const float dadz = -a * alpha * alpha;
+  // (1 - alpha) / Z = a alpha, so P = alpha w + a alpha score and dP/dZ =
+  // dalpha/dZ (w + a score): no 1.f - alpha, which cancels at small a Z
+  const float oz = a * alpha;
   for (int k = lane; k < D; k += kWave) s_v[wave][k] = 0.f;
   float A = 0.f, sbc = 0.f;
   for (int t = wave; t < L; t += 4) {
     const float c = cosv[b * L + t];
     const float score = 1.f - acosf(c) / kPi;
     const float wt = w[b * L + t];
-    const float P = alpha * wt + (1.f - alpha) * score / Z;
+    const float P = alpha * wt + oz * score;
     const float mp = mask[b * L + t] * (1.f / P);
-    const float dPdZ = wt * dadz - score * (dadz / Z + (1.f - alpha) / (Z * Z));
+    const float dPdZ = dadz * (wt + a * score);
     A += mp * dPdZ;
-    const float beta = mp * (1.f - alpha) / Z;
+    const float beta = mp * oz;
     const float st = sqrtf(1.f - c * c);
     sbc += beta * c / st;
     const float coef = beta / st;
@@ -446,7 +452,7 @@ extern "C" int mmb_word_logprob_forward(const float* latents, int64_t b, int d, 
                                         const float* mask, float a, int want_grad, void* ws,
                                         float* lp, float* state, float* gsum, float* cos_out,
                                         hipStream_t stream) {
-  MMB_REQUIRE(latents && wn && w && mask && lp && ws && b >= 0 && d > 0 && d <= 512 && v > 0 && l >= 0);
+  MMB_REQUIRE(latents && wn && w && mask && lp && ws && b >= 0 && d > 0 && d <= kWordMaxD && v > 0 && l >= 0);
   MMB_REQUIRE(ids ? (table != nullptr) : (sent_dense != nullptr || l == 0));
   MMB_REQUIRE(!want_grad || (state && gsum && cos_out));
   if (b == 0) return MMB_OK;
@@ -462,7 +468,7 @@ extern "C" int mmb_word_logprob_forward(const float* latents, int64_t b, int d, 
     MMB_ZCASE(14) MMB_ZCASE(15) MMB_ZCASE(16) MMB_ZCASE(17) MMB_ZCASE(18) MMB_ZCASE(19)
     MMB_ZCASE(20)
 #undef MMB_ZCASE
-    default: return MMB_EINVAL;  // d > 320
+    default: return MMB_EINVAL;  // not reached: d <= kWordMaxD
   }
   MMB_LAUNCH_CHECK();
   TokSrc tok{ids, table, sent_dense, v};
@@ -478,7 +484,7 @@ extern "C" int mmb_word_logprob_backward(const float* latents, int64_t b, int d,
                                          const float* mask, float a, const float* state,
                                          const float* gsum, const float* cosv, const float* dlp,
                                          float* dlat, hipStream_t stream) {
-  MMB_REQUIRE(latents && w && mask && state && gsum && cosv && dlp && dlat && d > 0 && d <= 512);
+  MMB_REQUIRE(latents && w && mask && state && gsum && cosv && dlp && dlat && d > 0 && d <= kWordMaxD);
   MMB_REQUIRE(ids ? (table != nullptr) : (sent_dense != nullptr || l == 0));
   if (b == 0) return MMB_OK;
   TokSrc tok{ids, table, sent_dense, v};

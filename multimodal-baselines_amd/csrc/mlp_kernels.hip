@@ -44,7 +44,7 @@ __device__ __forceinline__ int c_row(int r, int lane) { return (r & 3) + 8 * (r 
 
 constexpr int kTrWaves = 8;
 constexpr int kTrNT = kTrWaves * kWave;  // 512
-constexpr int kTrMaxFT = 2;              // 32-feature tiles per wave (d <= 512)
+constexpr int kTrMaxFT = 2;              // 32-feature tiles per wave
 constexpr int kTrMaxP = 16;              // hidden tiles = workgroups (h <= 512)
 constexpr int kTrMaxO = 16;              // outputs (n_out <= 16)
 
@@ -676,6 +676,17 @@ __global__ __launch_bounds__(256) void mlp_bwd_params_kernel(const float* __rest
   }
 }
 
+// Dynamic LDS of mlp_train_mc_kernel<nTd> with o outputs (the carve-up at the
+// kernel's top).  Two row buffers of 32 x (32 nTd + 1) floats are most of it:
+// with the 156 KB a launch may ask for (the kernel also has a static word)
+// nTd <= 14 fits for o <= 13 and nTd <= 13 for o = 14..16.
+constexpr size_t kTrLdsMax = 156 * 1024;
+static size_t train_lds_bytes(int nTd, int o) {
+  return sizeof(float) * (6 * kBatchMax + 2 * static_cast<size_t>(kBatchMax) * (32 * nTd + 1) +
+                          2 * kBatchMax * o + kTrWaves * kBatchMax * 32 + kBatchMax * 32 +
+                          kBatchMax * o + o * 32 + 32 + o + kTrWaves);
+}
+
 template <int NTD>
 static int launch_train_mc(const TrainArgs& a, size_t lds, hipStream_t stream) {
   // the dynamic LDS this launch needs (the kernel also has a static word, so
@@ -749,6 +760,13 @@ extern "C" size_t mmb_mlp_workspace_bytes(int d, int h) {
   return 16 + sizeof(float) * 2 * static_cast<size_t>(ceil_div(h, 32)) * kBatchMax * kTrMaxO;
 }
 
+extern "C" int mmb_mlp_train_max_d(int o) {
+  if (o < 1 || o > kTrMaxO) return 0;
+  int nTd = 0;
+  while (nTd < kTrWaves * kTrMaxFT && train_lds_bytes(nTd + 1, o) <= kTrLdsMax) ++nTd;
+  return 32 * nTd;
+}
+
 extern "C" int mmb_mlp_train(const float* latents, const float* labels, const int64_t* perm,
                              int64_t n_per_epoch, int n_epochs, int batch, int d, int h, int o,
                              float lr, float* w1, float* b1, float* w2, float* b2,
@@ -757,8 +775,8 @@ extern "C" int mmb_mlp_train(const float* latents, const float* labels, const in
                              float* valid_loss, void* ws, int32_t* flag, hipStream_t stream) {
   MMB_REQUIRE(latents && labels && perm && w1 && b1 && w2 && b2 && step_loss && ws);
   MMB_REQUIRE(n_per_epoch > 0 && n_epochs >= 0 && batch >= 1 && batch <= kBatchMax);
-  MMB_REQUIRE(d > 0 && d <= 32 * kTrWaves * kTrMaxFT && h > 0 && h <= 32 * kTrMaxP);
   MMB_REQUIRE(o >= 1 && o <= kTrMaxO && epoch0 >= 0);
+  MMB_REQUIRE(d > 0 && d <= mmb_mlp_train_max_d(o) && h > 0 && h <= 32 * kTrMaxP);
   MMB_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && (reinterpret_cast<uintptr_t>(latents) & 15) == 0);
   MMB_REQUIRE(d % 4 == 0);
   if (v_latents) {
@@ -778,10 +796,7 @@ extern "C" int mmb_mlp_train(const float* latents, const float* labels, const in
   a.nbv = v_latents ? static_cast<int>(ceil_div(n_valid, batch)) : 0;
   a.ctl = static_cast<unsigned*>(ws);
   a.xbuf = reinterpret_cast<float*>(static_cast<char*>(ws) + 16);
-  const size_t lds = sizeof(float) * (6 * kBatchMax + 2 * static_cast<size_t>(kBatchMax) * (32 * a.nTd + 1) +
-                                      2 * kBatchMax * o + kTrWaves * kBatchMax * 32 +
-                                      kBatchMax * 32 + kBatchMax * o + o * 32 + 32 + o + kTrWaves);
-  MMB_REQUIRE(lds <= 156 * 1024);
+  const size_t lds = train_lds_bytes(a.nTd, o);
   // the control words are zero when ws is first handed over and the last
   // workgroup leaves them zero (no memset node: see mmb_pc_solve_mc)
   switch (a.nTd) {
@@ -789,10 +804,9 @@ extern "C" int mmb_mlp_train(const float* latents, const float* labels, const in
     case n: return launch_train_mc<n>(a, lds, stream);
     MMB_TRAIN_NTD(1) MMB_TRAIN_NTD(2) MMB_TRAIN_NTD(3) MMB_TRAIN_NTD(4) MMB_TRAIN_NTD(5)
     MMB_TRAIN_NTD(6) MMB_TRAIN_NTD(7) MMB_TRAIN_NTD(8) MMB_TRAIN_NTD(9) MMB_TRAIN_NTD(10)
-    MMB_TRAIN_NTD(11) MMB_TRAIN_NTD(12) MMB_TRAIN_NTD(13) MMB_TRAIN_NTD(14) MMB_TRAIN_NTD(15)
-    MMB_TRAIN_NTD(16)
+    MMB_TRAIN_NTD(11) MMB_TRAIN_NTD(12) MMB_TRAIN_NTD(13) MMB_TRAIN_NTD(14)
 #undef MMB_TRAIN_NTD
-    default: return MMB_EINVAL;
+    default: return MMB_EINVAL;  // not reached: mmb_mlp_train_max_d(o) <= 448
   }
 }
 

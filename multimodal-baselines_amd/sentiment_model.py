@@ -253,7 +253,15 @@ def train_sentiment(args, model, train_data, train_latents, valid_data, valid_la
     vlab = _labels(valid_data, dev)
     in_kernel = valid_data.batch_size == B and n_valid > 0
     nbv = (n_valid + B - 1) // B if in_kernel else 0
-    ws = torch.zeros(L.query("mmb_mlp_workspace_bytes", d, h) // 4 + 4, dtype=torch.float32,
+    # mmb_mlp_train reads its rows as float4: a width that is no multiple of 4
+    # (GloVe 50) trains on rows and W1 padded with zero columns, which add
+    # nothing to any sum and get a zero gradient; W1 is copied back after
+    # every launch
+    dp = (d + 3) // 4 * 4
+    if dp != d:
+        lat = torch.nn.functional.pad(lat, (0, dp - d)).contiguous()
+        vlat = torch.nn.functional.pad(vlat, (0, dp - d)).contiguous()
+    ws = torch.zeros(L.query("mmb_mlp_workspace_bytes", dp, h) // 4 + 4, dtype=torch.float32,
                      device=dev)  # zeroed once: the launch leaves its control words zero
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
 
@@ -274,9 +282,13 @@ def train_sentiment(args, model, train_data, train_latents, valid_data, valid_la
         else:
             vloss = None
             vargs = (None, None, None, 0, 1, i, None)
-        L.call("mmb_mlp_train", L.ptr(lat), L.ptr(lab), L.ptr(perm), n_samples, block, B, d, h, o,
-               float(lr), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), L.ptr(step_loss), *vargs,
+        w1r = w1 if dp == d else torch.nn.functional.pad(w1.detach(), (0, dp - d)).contiguous()
+        L.call("mmb_mlp_train", L.ptr(lat), L.ptr(lab), L.ptr(perm), n_samples, block, B, dp, h, o,
+               float(lr), L.ptr(w1r), L.ptr(b1), L.ptr(w2), L.ptr(b2), L.ptr(step_loss), *vargs,
                L.ptr(ws), L.ptr(flag), L.stream_ptr())
+        if dp != d:
+            with torch.no_grad():
+                w1.copy_(w1r[:, :d])
         out = torch.cat([step_loss, vloss]) if vloss is not None else step_loss
         host = out.cpu().numpy()  # the one read-back of the stretch
         if int(flag.item()) & L.MMB_FLAG_SYNC_TIMEOUT:
