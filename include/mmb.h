@@ -238,6 +238,9 @@ int mmb_calc_weights(const float* x, int64_t rows, int f, const float* b_mean,
  *   aux[0][i]  = count_nonzero(w), aux[1][i] = sum_t w_t, aux[2][i] = the
  *                power-of-2 scale putting max|s[i,:]| in [2^14, 2^15) (planar
  *                [3][n]; aux[0] is the SIF count the Gram / removal kernels take)
+ * Widths: a modality row of whole float4 units (width % 4 == 0, 16-byte
+ * aligned base) may be up to 1280 floats wide, any other row up to 320;
+ * MMB_EINVAL before any launch past that (and with colmax at d > 640).
  * replaces the frame loops of sif2.estimate_embedding_overall_gpu2
  *   /root/reference/sif2.py:181-205 and the gathers at simplesif.py:862-871 */
 int mmb_mm2_stream(const int32_t* ids, const float* table, int64_t v, const float* wtab32,
@@ -256,7 +259,8 @@ int mmb_mm2_stream(const int32_t* ids, const float* table, int64_t v, const floa
  * fixed part order and writes the same outputs as mmb_mm2_stream (x, s in
  * the s_half format asked for, aux, colmax; n <= 8192 with colmax).  Rows are
  * deterministic and equal mmb_mm2_stream's to the f32 order of the token and
- * frame sums.
+ * frame sums (bit for bit with one range).  Widths as mmb_mm2_stream, and
+ * 3 d + 2 a + 2 vd <= 2240 (the second kernel's columns): MMB_EINVAL otherwise.
  * replaces: the frame loops of sif2.estimate_embedding_overall_gpu2
  *   /root/reference/sif2.py:181-205 at the per-split call sites
  *   /root/reference/simplesif.py:308-311 (POM's long transcripts)          */
@@ -334,14 +338,17 @@ size_t mmb_mm2_colmax_ws_bytes(int d);
 /* Padded width (row stride) of the per-utterance sums: roundup(2(d+a+vd), 32). */
 int mmb_mm2_k(int d, int a, int vd);
 
-/* Leading dimension of the merged projection: roundup(d+1, 64). */
+/* Leading dimension of the merged projection: roundup(d+1, 64).  The
+ * projections take ldw <= 384 (d <= 383); mmb_mm2_prepare and mmb_mm2_project
+ * return MMB_EINVAL past it, mmb_mm2_project_x3* past ldw = 320 (d <= 319). */
 int mmb_mm2_ldw(int d);
 
 /* Merge the 6 combinations' (W_mu, b_mu, W_log_sigma, b_log_sigma) into
  * wm [k, ldw] (ldw >= d+1; column d carries the total-weight row) and
  * c0 [ldw] for frame count t.  Pointer arrays are HOST arrays of DEVICE
  * pointers in key order audio, visual, audiovisual, textaudio, textvisual,
- * textaudiovisual (sif2.py:167-174).                                         */
+ * textaudiovisual (sif2.py:167-174).  d <= 383 (ldw <= 384: the widest wm a
+ * projection takes), MMB_EINVAL before any launch otherwise.                 */
 int mmb_mm2_prepare(const float* const* w_mu, const float* const* b_mu,
                     const float* const* w_ls, const float* const* b_ls, int d, int a, int vd,
                     int t, float* wm, int ldw, float* c0, void* wsplit, hipStream_t stream);

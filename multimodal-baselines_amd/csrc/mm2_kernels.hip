@@ -1095,6 +1095,9 @@ using namespace mmb;
 
 extern "C" int mmb_mm2_ldw(int d) { return (d + 1 + 63) / 64 * 64; }
 
+// widest merged projection any kernel takes (mm2_project_kernel<6>): d <= 383
+constexpr int kProjectMaxLdw = 384;
+
 extern "C" size_t mmb_mm2_split_bytes(int d, int a, int vd) {
   const size_t ldw = mmb_mm2_ldw(d), kp = mmb_mm2_k(d, a, vd);
   return 2 * ldw * kp * sizeof(_Float16) + ldw * sizeof(float);
@@ -1106,6 +1109,7 @@ extern "C" int mmb_mm2_prepare(const float* const* w_mu, const float* const* b_m
                                hipStream_t stream) {
   MMB_REQUIRE(w_mu && b_mu && w_ls && b_ls && wm && c0 && d > 0 && a > 0 && vd > 0 && t > 0);
   MMB_REQUIRE(ldw == mmb_mm2_ldw(d));
+  MMB_REQUIRE(ldw <= kProjectMaxLdw);  // d <= 383: no projection takes a wider wm
   PrepArgs p{};
   for (int k = 0; k < 6; ++k) {
     MMB_REQUIRE(w_mu[k] && b_mu[k] && w_ls[k] && b_ls[k]);
@@ -1235,7 +1239,7 @@ extern "C" int mmb_mm2_project(const float* s, const float* num, const float* au
                                const float* wm, int ldw, const float* c0, int64_t n, int k,
                                int d, float* out, hipStream_t stream) {
   MMB_REQUIRE(s && num && aux && wm && c0 && out && n >= 0 && d > 0);
-  MMB_REQUIRE(ldw == mmb_mm2_ldw(d) && k % 32 == 0);
+  MMB_REQUIRE(ldw == mmb_mm2_ldw(d) && ldw <= kProjectMaxLdw && k % 32 == 0);
   if (n == 0) return MMB_OK;
   switch (ldw / 64) {
     case 1: return launch_project<1>(s, num, aux, wm, c0, n, k, d, out, stream);

@@ -363,12 +363,20 @@ def mm2_dims(d, a, vd):
     return L.query("mmb_mm2_k", d, a, vd), L.query("mmb_mm2_ldw", d)
 
 
+# widest merged projection of libmmb (mmb_mm2_prepare / mmb_mm2_project: MMB_EINVAL past it)
+PROJECT_MAX_LDW = 384
+
+
 class MMB2Projection:
     """Merged [Kp, ldw] projection of the six generators (sif2.py:167-205)."""
 
     def __init__(self, networks: dict, d: int, a: int, vd: int, t: int, device):
         self.d, self.a, self.vd, self.t = d, a, vd, t
         self.kp, self.ldw = mm2_dims(d, a, vd)
+        if self.ldw > PROJECT_MAX_LDW:
+            raise L.MMBError(f"MMB2 projection: text width d = {d} (mmb_mm2_ldw(d) = {self.ldw}) is "
+                             f"past the widest merged projection libmmb takes, d <= "
+                             f"{PROJECT_MAX_LDW - 1} (ldw <= {PROJECT_MAX_LDW})")
         self.wm = torch.empty((self.kp, self.ldw), dtype=torch.float32, device=device)
         self.c0 = torch.empty((self.ldw,), dtype=torch.float32, device=device)
         nbytes = L.query("mmb_mm2_split_bytes", d, a, vd)
@@ -479,6 +487,10 @@ def split_ws(n: int, t: int, d: int, a: int, vd: int, device, parts: int = 0) ->
     return torch.empty(max(nb, 16), dtype=torch.uint8, device=device)
 
 
+# widest modality row of the stream kernels (mmb_mm2_stream: MMB_EINVAL past it)
+STREAM_MAX_VECTOR_WIDTH, STREAM_MAX_SCALAR_WIDTH = 1280, 320
+
+
 def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=None,
                text_dense=None, emb_dense=None, w_dense=None, flag=None, out=None,
                s_half: bool = True, colmax=None, colmax_ws=None, split=None, parts: int = 0):
@@ -494,6 +506,13 @@ def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=Non
     part order (mmb_mm2_stream_split: a few long rows, POM's splits)."""
     kp, _ = mm2_dims(d, a, vd)
     dev = audio.device
+    text_src = table if ids32 is not None else text_dense
+    for what, w, src in (("text", d, text_src), ("audio", a, audio), ("visual", vd, visual)):
+        vec = w % 4 == 0 and src is not None and src.data_ptr() % 16 == 0
+        if w > (STREAM_MAX_VECTOR_WIDTH if vec else STREAM_MAX_SCALAR_WIDTH):
+            raise L.MMBError(f"mm2_stream: {what} width {w} is past the stream kernels' limit: "
+                             f"{STREAM_MAX_VECTOR_WIDTH} for rows of whole float4 units (width % 4 "
+                             f"== 0, 16-byte aligned), {STREAM_MAX_SCALAR_WIDTH} otherwise")
     if out is None:
         out = (torch.empty((n, d), dtype=torch.float32, device=dev),
                s_buffer(n, kp, s_half, dev),

@@ -56,6 +56,79 @@ def estimate_embedding_overall_gpu2(data, params, sentence_weights, embeddings, 
     return cs
 
 
+def total_weight(data, params, sentence_weights, dtype=np.float64):
+    """(total, absolute): the total weight of sif2.py:186-188 per utterance, and
+    the sum of |sentence weights| + |q_mean| + |q_sigma| over every key that it
+    is the signed sum of (absolute / |total| is its cancellation)."""
+    c = lambda a: np.asarray(a, dtype=dtype)
+    sw = c(sentence_weights)
+    total, absolute = sw.sum(-1), np.abs(sw).sum(-1)
+    for k in KEYS:
+        Wm, bm, Wl, bl = params[k]
+        qm, qs = calc_weights(c(data[k]), c(bm), c(bl))
+        total = total + qm.sum(-1).sum(-1) + qs.sum(-1).sum(-1)
+        absolute = absolute + np.abs(qm).sum(-1).sum(-1) + np.abs(qs).sum(-1).sum(-1)
+    return total, absolute
+
+
+def _segments(key, D, A, Vd):
+    """(modality 0 text / 1 audio / 2 visual, offset in the key's features, width)."""
+    segs, off = [], 0
+    for m, w in ((0, D if key.startswith("text") else 0), (1, A if "audio" in key else 0),
+                 (2, Vd if "visual" in key else 0)):
+        if w:
+            segs.append((m, off, w))
+            off += w
+    return segs
+
+
+def frame_sums(text, audio, visual):
+    """(s, s_abs) in f64: the per-utterance sums over the frames [Sx_t | Sxx_t |
+    Sx_a | Sxx_a | Sx_v | Sxx_v] ([N, 2 (D + A + Vd)]) that the closed form
+    projects, and the sums of the terms' absolute values."""
+    parts, absolute = [], []
+    for x in (text, audio, visual):
+        x = np.asarray(x, np.float64)
+        parts += [x.sum(1), (x * x).sum(1)]
+        absolute += [np.abs(x).sum(1), (x * x).sum(1)]
+    return np.concatenate(parts, -1), np.concatenate(absolute, -1)
+
+
+def merged_projection(params, D, A, Vd, T):
+    """(Wm [K, D + 1], c0 [D + 1], Wm_abs, c0_abs) in f64: the twelve
+    projections of sif2.py:200-205 and the total weight (:186-188, column D)
+    folded over the frame sums of frame_sums().  With a = exp(-2 b_ls) and
+    b = b_mu of feature f of key k (q_mean = a (x - b), q_sigma = a (x - b)^2
+    - 1 summed over T frames):
+      Sx row   of f: sum_k a (W_mu[f] - 2 b W_ls[f])     | column D: a (1 - 2 b)
+      Sxx row  of f: sum_k a W_ls[f]                     | column D: a
+      c0           : T sum_k sum_f (-a b W_mu[f] + a b^2 W_ls[f] - W_ls[f])
+                                                         | column D: -a b + a b^2 - 1
+    The *_abs arrays sum the absolute values of the same terms."""
+    w = (D, A, Vd)
+    base = (0, 2 * D, 2 * D + 2 * A)
+    K = 2 * (D + A + Vd)
+    Wm, Wa = np.zeros((K, D + 1)), np.zeros((K, D + 1))
+    c0, ca = np.zeros(D + 1), np.zeros(D + 1)
+    for k in KEYS:
+        Wmu, bmu, Wls, bls = (np.asarray(p, np.float64) for p in params[k])
+        for m, off, wid in _segments(k, D, A, Vd):
+            sl = slice(off, off + wid)
+            a = np.exp(-2.0 * bls[sl])[:, None]
+            b = bmu[sl][:, None]
+            mu1 = np.concatenate([Wmu[sl], np.ones((wid, 1))], 1)  # column D: weight 1
+            ls1 = np.concatenate([Wls[sl], np.ones((wid, 1))], 1)
+            rx = slice(base[m], base[m] + w[m])
+            rxx = slice(base[m] + w[m], base[m] + 2 * w[m])
+            Wm[rx] += a * (mu1 - 2.0 * b * ls1)
+            Wa[rx] += np.abs(a * mu1) + np.abs(2.0 * a * b * ls1)
+            Wm[rxx] += a * ls1
+            Wa[rxx] += np.abs(a * ls1)
+            c0 += T * (-a * b * mu1 + a * b * b * ls1 - ls1).sum(0)
+            ca += T * (np.abs(a * b * mu1) + np.abs(a * b * b * ls1) + np.abs(ls1)).sum(0)
+    return Wm, c0, Wa, ca
+
+
 def params_from_module(gen):
     """{key: (W_mu, b_mu, W_ls, b_ls)} numpy f32 from an AudioVisualGeneratorMultimodal."""
     out = {}
