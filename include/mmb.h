@@ -119,6 +119,13 @@ int mmb_xt_omega(const float* num, const float* cnt, int64_t n, int d, const dou
  * pc_out [npc, d] float64.  d <= 512, k <= min(16, d): a block wider than the
  * space has singular k x k factors and is rejected (MMB_EINVAL, as in the two
  * entry points below); its first d columns already span everything.
+ * Accuracy (all three solve entry points; tests/test_gpu_spectrum.py): the
+ * first component stays within 1e-12 of the reference's up to l1/l11 = 1e10
+ * and down to l1/l2 - 1 = 1e-4 (1e-10 at 1e-6: eps / gap).  The solve sees X
+ * only through G, so component c carries about eps * l1/lc whatever the
+ * kernel does: 2e-12 at l1/l2 = 6e4, 1e-10 at 6e6, 2e-8 at 6e8 for the second
+ * one (the CPU oracle's Gram route measures the same).  A caller who needs
+ * later components beyond that on such a spectrum needs the rows, not G.
  * replaces: sif_functions.compute_pc /root/reference/sif_functions.py:58-67 */
 int mmb_pc_solve(const double* g, int d, const double* z0, int k, int npc, int n_iter,
                  int transposed, double* pc_out, hipStream_t stream);

@@ -1411,8 +1411,15 @@ __device__ __forceinline__ double rsqrt_f64(double x) {
 // sqrt(d_jj), and w[m - 1] <- w[m] - l_ij l_(j+m)j (a readlane of lane j + m).  The substitution is right-looking in the same
 // shifted form: lane c's t = e_c, step i: x_i = t_0 / L_ii to LDS, t_(m-1) <-
 // t_m - L_(i+m)i x_i (column i of L as LDS broadcasts).
+//
+// REL: *fail is also set where a pivot is not above tau times its diagonal
+// entry dg (lane j: W_jj).  That ratio is sin^2 of the angle between column
+// j of the block and the columns before it: below it the factor is positive
+// but Z = B L^-T cancels 1 / sqrt(ratio) digits of B.
+template <bool REL = false>
 __device__ __forceinline__ void p16_chol_regs(double (&w)[kMaxK], double* sL, double* sLi, int k,
-                                              int lane, int* fail, double (&x)[kMaxK], int mark = 31) {
+                                              int lane, int* fail, double (&x)[kMaxK], int mark = 31,
+                                              double dg = 0.0, double tau = 0.0) {
   double* rl = sLi + kMaxK * kMaxK - kMaxK;  // the reciprocal pivots: sLi's last row until the end
   bool bad = false;
   PC_WMARK(mark);
@@ -1420,6 +1427,7 @@ __device__ __forceinline__ void p16_chol_regs(double (&w)[kMaxK], double* sL, do
   for (int j = 0; j < k; ++j) {
     const double djj = readlane_f64(w[0], j);
     bad = bad || !(djj > 0.0);
+    if constexpr (REL) bad = bad || !(djj > tau * readlane_f64(dg, j));
     const double p = djj > 0.0 ? djj : 1.0;
     const double r = rsqrt_f64(p);
     const double lij = (lane == j) ? p * r : (lane > j ? w[0] * r : 0.0);
@@ -1902,10 +1910,14 @@ __device__ __forceinline__ void p16_rmul(const double* In, const double* M, doub
 // neither which blocks factor nor the span Z keeps; it only put ~1 us of
 // broadcasts and scalings on the round's critical path.  d is then not
 // written (the MGS^2 fallback forms its scales from W).
-template <bool EQ = true>
+// REL: a pivot at or below tau times its diagonal entry of W also sets *fail
+// (p16_chol_regs).
+template <bool EQ = true, bool REL = false>
 __device__ __forceinline__ void p16_eq_chol(const double* W, double* L, double* Li, double* M,
-                                            double* d, int k, int lane, int* fail, double* Mt = nullptr) {
+                                            double* d, int k, int lane, int* fail, double* Mt = nullptr,
+                                            double tau = 0.0) {
   double w[kMaxK], x[kMaxK];
+  const double dg = (REL && !EQ && lane < k) ? W[lane * k + lane] : 1.0;  // (equilibrated: 1)
   PC_WMARK(30);
 #pragma unroll
   for (int m = 0; m < kMaxK; ++m) w[m] = (lane < k && m < k) ? W[lane * k + m] : 0.0;
@@ -1917,7 +1929,7 @@ __device__ __forceinline__ void p16_eq_chol(const double* W, double* L, double* 
     if (lane < kMaxK) d[lane] = lane < k ? di : 0.0;
   }
   if (lane == 0) *fail = 0;
-  p16_chol_regs(w, L, Li, k, lane, fail, x, 37);  // probe marks 37-39
+  p16_chol_regs<REL>(w, L, Li, k, lane, fail, x, 37, dg, tau);  // probe marks 37-39
   if (lane < kP16W) {  // lane c: column c of L^-1 diag(d)
 #pragma unroll
     for (int i = 0; i < kP16W; ++i) {
@@ -2038,6 +2050,14 @@ constexpr int kPnNW = kPnNT / kWave;                   // 8
 constexpr int kPnPw = kPnNW - 1;                       // waves holding G (the last one factors)
 constexpr int kPnKs = (kP16MaxD / 4 + kPnPw - 1) / kPnPw;  // k-steps of G per wave (12)
 constexpr int kPnGu = (kPmMaxT * 256 + kPnPw * kWave - 1) / (kPnPw * kWave);  // gather loads per thread (12)
+// The direct branch's last factor: the smallest pivot / diagonal ratio at
+// which the implicit round (raw products times M^T) still enters the tail;
+// below it the explicit MGS^2 block does.  The first component then stays
+// within ~eps / sqrt(ratio) = 1e-13 of the oracle; at n_iter = 7 mild
+// spectra (l1/l11 <= ~300) leave this ratio at 0.7 to 1, so they never take
+// the fallback (it fires from about l1/l2 = 1e5, or l1/l11 = 1e8 spread
+// evenly).
+constexpr double kPnTailPivot = 1e-6;
 
 // ABL (tools build only, timing ablations, results invalid): 1 skips the
 // round's B_{r+1} / W_{r+1} update, 2 skips the round's factor
@@ -2380,8 +2400,14 @@ __global__ __launch_bounds__(kPnNT) void pc_solve_mc_kernel(const double* __rest
     // factor held, returns the counter to zero.  A failed factor (pivot <= 0)
     // falls through to the explicit MGS^2 block below with exchange x + 1:
     // every workgroup is still there (they return only after the join).
+    // So does a factor with a pivot at or below kPnTailPivot of its diagonal
+    // entry: Z = B M^T and G Z = H M^T then cancel 1 / sqrt(ratio) digits of
+    // the raw B and H, and no later product damps what the tail's W and H
+    // get from that (a dominant first component and few iterations -- the
+    // block after a squared round straight into the tail: 1e-11 in the first
+    // component at l1/l11 = 1e6, n_iter = 3, with every pivot positive).
     if (wave == kPnPw) {
-      p16_eq_chol<false>(sW, sL, sLi, sM, sd, k, lane, &s_fail, sM2);
+      p16_eq_chol<false, true>(sW, sL, sLi, sM, sd, k, lane, &s_fail, sM2, kPnTailPivot);
     } else {
       tile_partials(sY);
       bar_pw();
