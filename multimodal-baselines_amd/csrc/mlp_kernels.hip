@@ -777,11 +777,11 @@ extern "C" int mmb_mlp_train(const float* latents, const float* labels, const in
   MMB_REQUIRE(n_per_epoch > 0 && n_epochs >= 0 && batch >= 1 && batch <= kBatchMax);
   MMB_REQUIRE(o >= 1 && o <= kTrMaxO && epoch0 >= 0);
   MMB_REQUIRE(d > 0 && d <= mmb_mlp_train_max_d(o) && h > 0 && h <= 32 * kTrMaxP);
-  MMB_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && (reinterpret_cast<uintptr_t>(latents) & 15) == 0);
+  MMB_REQUIRE(aligned16(ws) && aligned16(latents));
   MMB_REQUIRE(d % 4 == 0);
   if (v_latents) {
     MMB_REQUIRE(v_labels && v_perm && valid_loss && n_valid > 0 && valid_every > 0);
-    MMB_REQUIRE((reinterpret_cast<uintptr_t>(v_latents) & 15) == 0);
+    MMB_REQUIRE(aligned16(v_latents));
   }
   if (n_epochs == 0) return MMB_OK;
   TrainArgs a{};
@@ -820,13 +820,8 @@ extern "C" int mmb_mlp_forward_train(const float* x, int64_t b, int d, int h, in
   MMB_REQUIRE(lds <= 64 * 1024);
   const int grid = static_cast<int>(ceil_div(b, kMlpRows));
   const size_t lds_w = lds + sizeof(float) * static_cast<size_t>(h) * mlp_wld(d);
-  if (d % 4 == 0 && (reinterpret_cast<uintptr_t>(w1) & 15) == 0 && lds_w <= 160 * 1024) {
-    static bool attr_set = false;  // > 64 KB of dynamic LDS (the regressor: 134 KB)
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_rows_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_set = true;
-    }
+  if (d % 4 == 0 && aligned16(w1) && lds_w <= 160 * 1024) {
+    allow_dynamic_lds<&mlp_fwd_rows_kernel<true>>(160 * 1024);  // (the regressor: 134 KB)
     mlp_fwd_rows_kernel<true><<<grid, 256, lds_w, stream>>>(x, b, d, h, o, w1, b1, w2, b2, y_out,
                                                            hid_out);
   } else {

@@ -350,7 +350,7 @@ __global__ void mm2_split_wm_pieces_kernel(const float* __restrict__ wm, int ldw
   for (int m = 0; m < 3; ++m) {
     src0[m] = sb;
     dst0[m] = db;
-    kq[m] = (2 * w[m] + 31) / 32 * 32;
+    kq[m] = piece_k(w[m]);
     sb += 2 * w[m];
     db += kq[m];
   }
@@ -1052,19 +1052,12 @@ static int launch_project_x3(const _Float16* s, const float* num, const float* a
   const int grid = static_cast<int>(ceil_div(n, kXM));
   constexpr size_t ldsb = x3b_lds_bytes<CT>();
   static_assert(ldsb <= 160 * 1024, "x3b chunk rings exceed LDS");
-  static bool attr_b = false;
-  if (!attr_b) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mm2_project_x3b_kernel<CT, false, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsb));
-    if constexpr (CT == 5)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mm2_project_x3b_kernel<CT, true, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsb));
-    attr_b = true;
-  }
-  auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  allow_dynamic_lds<&mm2_project_x3b_kernel<CT, false, true>>(ldsb);
+  if constexpr (CT == 5) allow_dynamic_lds<&mm2_project_x3b_kernel<CT, true, true>>(ldsb);
   // the row-wise epilogue: D in [256, 320) (column D in a lane's second
   // unit), whole float4 units, 16-byte aligned rows
-  const bool rowepi = d >= 256 && d % 4 == 0 && a16(num) && a16(out) && (sif == nullptr || a16(sif));
+  const bool rowepi = d >= 256 && d % 4 == 0 && aligned16(num) && aligned16(out) &&
+                      (sif == nullptr || aligned16(sif));
   if constexpr (CT == 5) {
     if (rowepi) {
       mm2_project_x3b_kernel<CT, true, true><<<grid, kXT, ldsb, stream>>>(s, num, aux, img, ci, c0,
@@ -1144,25 +1137,40 @@ extern "C" int mmb_mm2_prepare(const float* const* w_mu, const float* const* b_m
   return MMB_OK;
 }
 
+// The x3 projections' operands: the split sums s, the split weight image and
+// the column scales behind it.  Checked: every pointer given, the image's
+// shape (ldw of d, whole 32-deep chunks), 16-byte aligned s and image, and
+// sif_out given exactly with pc.
+struct X3Operands {
+  const _Float16 *s, *img;
+  const float* ci;
+};
+static int x3_operands(const void* s_split, const float* num, const float* aux, const void* wsplit,
+                       int ldw, const float* c0, int64_t n, int k, int d, const float* out,
+                       const double* pc, const float* sif_out, X3Operands* o) {
+  MMB_REQUIRE(s_split && num && aux && wsplit && c0 && out && n >= 0 && d > 0);
+  MMB_REQUIRE(ldw == mmb_mm2_ldw(d) && k % 32 == 0 && k >= 32);
+  MMB_REQUIRE((pc == nullptr) == (sif_out == nullptr));
+  MMB_REQUIRE(aligned16(s_split) && aligned16(wsplit));
+  o->s = static_cast<const _Float16*>(s_split);
+  o->img = static_cast<const _Float16*>(wsplit);
+  o->ci = reinterpret_cast<const float*>(o->img + 2 * static_cast<size_t>(ldw) * k);
+  return MMB_OK;
+}
+
 extern "C" int mmb_mm2_project_x3_rmpc(const void* s_split, const float* num, const float* aux,
                                        const void* wsplit, int ldw, const float* c0, int64_t n,
                                        int k, int d, float* out, const double* pc, float* sif_out,
                                        hipStream_t stream) {
-  MMB_REQUIRE(s_split && num && aux && wsplit && c0 && out && n >= 0 && d > 0);
-  MMB_REQUIRE(ldw == mmb_mm2_ldw(d) && k % 32 == 0 && k >= 32);
-  MMB_REQUIRE((pc == nullptr) == (sif_out == nullptr));
-  MMB_REQUIRE((reinterpret_cast<uintptr_t>(s_split) & 15) == 0 &&
-              (reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
+  X3Operands o;
+  if (const int rc = x3_operands(s_split, num, aux, wsplit, ldw, c0, n, k, d, out, pc, sif_out, &o)) return rc;
   if (n == 0) return MMB_OK;
-  const _Float16* s = static_cast<const _Float16*>(s_split);
-  const _Float16* img = static_cast<const _Float16*>(wsplit);
-  const float* ci = reinterpret_cast<const float*>(img + 2 * static_cast<size_t>(ldw) * k);
   switch (ldw / 64) {
-    case 1: return launch_project_x3<1>(s, num, aux, img, ci, c0, n, k, d, out, pc, sif_out, stream);
-    case 2: return launch_project_x3<2>(s, num, aux, img, ci, c0, n, k, d, out, pc, sif_out, stream);
-    case 3: return launch_project_x3<3>(s, num, aux, img, ci, c0, n, k, d, out, pc, sif_out, stream);
-    case 4: return launch_project_x3<4>(s, num, aux, img, ci, c0, n, k, d, out, pc, sif_out, stream);
-    case 5: return launch_project_x3<5>(s, num, aux, img, ci, c0, n, k, d, out, pc, sif_out, stream);
+    case 1: return launch_project_x3<1>(o.s, num, aux, o.img, o.ci, c0, n, k, d, out, pc, sif_out, stream);
+    case 2: return launch_project_x3<2>(o.s, num, aux, o.img, o.ci, c0, n, k, d, out, pc, sif_out, stream);
+    case 3: return launch_project_x3<3>(o.s, num, aux, o.img, o.ci, c0, n, k, d, out, pc, sif_out, stream);
+    case 4: return launch_project_x3<4>(o.s, num, aux, o.img, o.ci, c0, n, k, d, out, pc, sif_out, stream);
+    case 5: return launch_project_x3<5>(o.s, num, aux, o.img, o.ci, c0, n, k, d, out, pc, sif_out, stream);
     default: return MMB_EINVAL;  // d >= 320: the chunk rings exceed the 160 KB LDS
   }
 }
@@ -1195,35 +1203,26 @@ extern "C" int mmb_mm2_project_x3_split(const void* s_split, const float* num, c
   MMB_REQUIRE(slices >= 0);
   const int nsl = slices > 0 ? std::min({slices, std::max(1, k / kXK), kXSplitMax})
                              : mmb_mm2_project_x3_split_slices(n, k);
-  auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  const bool rowepi = ldw == 320 && ldw == mmb_mm2_ldw(d) && d >= 256 && d % 4 == 0 && a16(num) &&
-                      a16(out) && (sif_out == nullptr || a16(sif_out));
+  const bool rowepi = ldw == 320 && ldw == mmb_mm2_ldw(d) && d >= 256 && d % 4 == 0 && aligned16(num) &&
+                      aligned16(out) && (sif_out == nullptr || aligned16(sif_out));
   if (nsl < 2 || !rowepi || n <= 0)  // nothing to split: the one-pass kernel
     return mmb_mm2_project_x3_rmpc(s_split, num, aux, wsplit, ldw, c0, n, k, d, out, pc, sif_out, stream);
-  MMB_REQUIRE(s_split && num && aux && wsplit && c0 && out && k % 32 == 0 && k >= 32);
-  MMB_REQUIRE((pc == nullptr) == (sif_out == nullptr));
-  MMB_REQUIRE(a16(s_split) && a16(wsplit) && a16(ws));
+  // (the fall-back is decided before the workspace is looked at)
+  X3Operands o;
+  if (const int rc = x3_operands(s_split, num, aux, wsplit, ldw, c0, n, k, d, out, pc, sif_out, &o)) return rc;
   const int64_t tiles = ceil_div(n, kXM);
-  MMB_REQUIRE(ws && ws_bytes >= static_cast<size_t>(tiles) * nsl * kXM * 320 * sizeof(float));
+  MMB_REQUIRE(ws && aligned16(ws) && ws_bytes >= static_cast<size_t>(tiles) * nsl * kXM * 320 * sizeof(float));
   MMB_REQUIRE(tiles * nsl <= (int64_t{1} << 31) - 1);
-  const _Float16* s = static_cast<const _Float16*>(s_split);
-  const _Float16* img = static_cast<const _Float16*>(wsplit);
-  const float* ci = reinterpret_cast<const float*>(img + 2 * static_cast<size_t>(ldw) * k);
   constexpr size_t ldsb = x3b_lds_bytes<5>();
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mm2_project_x3b_kernel<5, true, true, 0, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsb));
-    attr = true;
-  }
+  allow_dynamic_lds<&mm2_project_x3b_kernel<5, true, true, 0, true>>(ldsb);
   const int cps = static_cast<int>(ceil_div(k / kXK, nsl));  // chunks per slice
   const int nse = static_cast<int>(ceil_div(k / kXK, cps));   // slices holding >= 1 chunk (<= nsl)
   f32x4* part = static_cast<f32x4*>(ws);
   mm2_project_x3b_kernel<5, true, true, 0, true><<<static_cast<unsigned>(tiles * nse), kXT, ldsb, stream>>>(
-      s, num, aux, img, ci, c0, n, k, d, out, pc, sif_out, nse, cps, part);
+      o.s, num, aux, o.img, o.ci, c0, n, k, d, out, pc, sif_out, nse, cps, part);
   MMB_LAUNCH_CHECK();
   x3_splitk_rows_kernel<<<static_cast<unsigned>(ceil_div(n, 4)), 256, 0, stream>>>(
-      reinterpret_cast<const float*>(part), nse, num, aux, ci, c0, n, d, out, pc, sif_out);
+      reinterpret_cast<const float*>(part), nse, num, aux, o.ci, c0, n, d, out, pc, sif_out);
   MMB_LAUNCH_CHECK();
   return MMB_OK;
 }
@@ -1252,10 +1251,7 @@ extern "C" int mmb_mm2_project(const float* s, const float* num, const float* au
   }
 }
 
-static int mm2_pieces_k(int d, int a, int vd) {
-  auto q = [](int w) { return (2 * w + 31) / 32 * 32; };
-  return q(d) + q(a) + q(vd);
-}
+static int mm2_pieces_k(int d, int a, int vd) { return piece_k(d) + piece_k(a) + piece_k(vd); }
 
 extern "C" size_t mmb_mm2_split_pieces_bytes(int d, int a, int vd) {
   const size_t ldw = mmb_mm2_ldw(d), kq = mm2_pieces_k(d, a, vd);
@@ -1359,8 +1355,7 @@ extern "C" size_t mmb_mm2_text_cache_bytes(int64_t v, int d) {
 extern "C" int mmb_mm2_text_cache(const float* table, int64_t v, int d, const float* wtab32,
                                   const float* wm, int ldw, void* cache, hipStream_t stream) {
   MMB_REQUIRE(table && wtab32 && wm && cache && v > 0 && v <= kTextMaxV);
-  MMB_REQUIRE(d > 0 && d % 4 == 0 && d + 1 <= kTextLdp && ldw > d &&
-              (reinterpret_cast<uintptr_t>(cache) & 15) == 0);
+  MMB_REQUIRE(d > 0 && d % 4 == 0 && d + 1 <= kTextLdp && ldw > d && aligned16(cache));
   float* ptab = static_cast<float*>(cache);
   int32_t* hot_slot1 = reinterpret_cast<int32_t*>(ptab + static_cast<size_t>(v) * kTextLdq);
   int32_t* hot_ids = hot_slot1 + v;

@@ -135,6 +135,29 @@ __host__ __device__ constexpr int x3_swz(int r) { return (0x78 >> (2 * ((r >> 2)
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// 16-byte alignment: what every float4 / b128 access of a row base needs
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// K rows of one modality's piece [Sx_m | Sxx_m] (2 w sums) in the piece-
+// ordered weight image, padded to whole 32-deep chunks.  The image's writer
+// (mmb_mm2_split_pieces) and its readers (the two fused kernels' entry
+// points) must agree on it; mmb_mm2_k rounds the SUM of the widths instead.
+__host__ __device__ constexpr int piece_k(int w) { return (2 * w + 31) / 32 * 32; }
+
+// Allows Kernel `bytes` of dynamic LDS (more than the default 64 KB), once per
+// process, before its first launch.  One flag per kernel: every kernel
+// (instantiation) is its own instantiation of this function.  A failure shows
+// at the launch that follows, so the call's return is not looked at.
+// (static: the flags stay out of the library's exported symbols)
+template <auto Kernel>
+static void allow_dynamic_lds(size_t bytes) {
+  static bool done = false;
+  if (done) return;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+  done = true;
+}
+
 // Zero n 32-bit words with a kernel (probe_kernels.hip).  Used wherever the
 // library must clear a buffer on the caller's stream: a hipMemsetAsync
 // captured into a HIP graph wrote address-like garbage into its destination

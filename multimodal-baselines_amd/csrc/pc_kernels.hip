@@ -2841,18 +2841,13 @@ static Gram2Plan gram_i8_plan(int64_t n, int d) {
 
 static size_t gram2_lds() {
   const size_t lds = sizeof(double) * 2 * kG2Rows * kG2Stride;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_tri_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    attr = true;
-  }
+  allow_dynamic_lds<&gram_tri_kernel>(lds);
   return lds;
 }
 
 static bool gram2_ok(const float* num, int d) {
   // 16-wave tile kernel: d <= 320 (20 tile rows, <= 8 tiles per wave per half)
-  return d % 4 == 0 && d <= 320 && (reinterpret_cast<uintptr_t>(num) & 15) == 0;
+  return d % 4 == 0 && d <= 320 && aligned16(num);
 }
 
 
@@ -3033,12 +3028,7 @@ static GramLPlan gram_i8l_plan(int64_t n, int d) {
 template <int DIAG, class S>
 static size_t gram_i8l_lds() {
   const size_t lds = 2 * kGiDig * kGiF * kGiRows;  // 160 KB: double-buffered digits
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_i8l_kernel<DIAG, S>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    attr = true;
-  }
+  allow_dynamic_lds<&gram_i8l_kernel<DIAG, S>>(lds);
   return lds;
 }
 
@@ -3224,13 +3214,7 @@ extern "C" int mmb_pc_solve(const double* g, int d, const double* z0, int k, int
   MMB_REQUIRE(k <= d);
   if (d <= kP16MaxD) {
     const size_t lds = p16_lds_bytes(d);
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_solve16_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(p16_lds_bytes(kP16MaxD)));
-      attr = true;
-    }
+    allow_dynamic_lds<&pc_solve16_kernel>(p16_lds_bytes(kP16MaxD));  // once, for the widest d
     pc_solve16_kernel<<<1, kP16NT, lds, stream>>>(g, d, z0, k, npc, n_iter, transposed, pc_out);
   } else {
     pc_solve_kernel<<<1, kSolveNT, 0, stream>>>(g, d, z0, k, npc, n_iter, transposed, pc_out);
@@ -3280,7 +3264,7 @@ extern "C" int mmb_pc_solve_mc(const double* g, int d, const double* z0, int k, 
                                hipStream_t stream) {
   MMB_REQUIRE(g && z0 && pc_out && ws && d > 1 && d <= kP16MaxD && k >= 1 && k <= kP16W);
   MMB_REQUIRE(npc >= 1 && npc <= k && n_iter >= 0 && k <= d);  // (k <= d: as mmb_pc_solve)
-  MMB_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0);
+  MMB_REQUIRE(aligned16(ws));
   return launch_solve_mc(g, d, z0, k, npc, n_iter, transposed, pc_out, ws, flag, false, stream);
 }
 
@@ -3289,7 +3273,7 @@ extern "C" int mmb_pc_solve_mc_xt(const double* g, int d, const float* x, int64_
                                   void* ws, int32_t* flag, hipStream_t stream) {
   MMB_REQUIRE(g && x && omega && pc_out && ws && d > 1 && d <= kP16MaxD && k >= 1 && k <= kP16W);
   MMB_REQUIRE(n >= 1 && n < d && n <= kXtMaxN && npc >= 1 && npc <= k && n_iter >= 0 && k <= d);
-  MMB_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0);
+  MMB_REQUIRE(aligned16(ws));
   const int T = (d + 15) / 16;
   double* g2 = reinterpret_cast<double*>(static_cast<char*>(ws) + 16) + static_cast<size_t>(2) * (d / 16 + 1) * 512;
   double* z0 = g2 + static_cast<size_t>(d) * d;
@@ -3316,13 +3300,7 @@ static int launch_solve_mc(const double* g, int d, const double* z0, int k, int 
   } else if (!g2_ready) {
     nsq_wg = (T * (T + 1) / 2 + kSqPerWg - 1) / kSqPerWg;
   }
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_solve_mc_kernel<0>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(p16_lds_bytes(kP16MaxD)));
-    attr = true;
-  }
+  allow_dynamic_lds<&pc_solve_mc_kernel<0>>(p16_lds_bytes(kP16MaxD));  // once, for the widest d
   // no memset node here: the counter / abort words must be zero when the
   // caller first hands ws over, and a completed solve leaves them zero.  The
   // r04 launcher enqueued a 16-byte hipMemsetAsync of them instead; captured
@@ -3354,8 +3332,7 @@ extern "C" int mmb_pc_remove(const float* num, const float* cnt, int64_t n, int 
   MMB_REQUIRE(num && pc && n >= 0 && d > 0 && npc >= 1 && ((out32 != nullptr) != (out64 != nullptr)));
   MMB_REQUIRE(static_cast<size_t>(npc) * d * sizeof(double) <= 64 * 1024);
   if (n == 0) return MMB_OK;
-  const bool v4 = (d % 4 == 0) && ((reinterpret_cast<uintptr_t>(num) & 15) == 0) &&
-                  (out32 == nullptr || (reinterpret_cast<uintptr_t>(out32) & 15) == 0);
+  const bool v4 = (d % 4 == 0) && aligned16(num) && (out32 == nullptr || aligned16(out32));
   const int U = v4 ? d / 4 : d;
   const int per = static_cast<int>(ceil_div(U, kWave));
   const int rr = remove_rows();

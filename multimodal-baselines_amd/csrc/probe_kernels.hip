@@ -109,7 +109,7 @@ using namespace mmb;
 extern "C" int mmb_probe_copy(const void* src, void* dst, int64_t bytes, int blocks, int nt,
                               hipStream_t stream) {
   MMB_REQUIRE(src && dst && bytes > 0 && bytes % 16 == 0 && blocks > 0);
-  MMB_REQUIRE(reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0);
+  MMB_REQUIRE(aligned16(src) && aligned16(dst));
   const int64_t n4 = bytes / 16;
   if (nt)
     probe_copy_kernel<true><<<probe_grid(n4, blocks), kProbeThreads, 0, stream>>>(
@@ -124,7 +124,7 @@ extern "C" int mmb_probe_copy(const void* src, void* dst, int64_t bytes, int blo
 extern "C" int mmb_probe_read(const void* src, int64_t bytes, int blocks, int nt, uint32_t* sink,
                               hipStream_t stream) {
   MMB_REQUIRE(src && sink && bytes > 0 && bytes % 16 == 0 && blocks > 0);
-  MMB_REQUIRE(reinterpret_cast<uintptr_t>(src) % 16 == 0);
+  MMB_REQUIRE(aligned16(src));
   const int64_t n4 = bytes / 16;
   if (nt)
     probe_read_kernel<true><<<probe_grid(n4, blocks), kProbeThreads, 0, stream>>>(

@@ -1357,6 +1357,20 @@ __global__ __launch_bounds__(1024) void colmax_reduce_kernel(const float* __rest
 // MMB_HOOK_* point below the product library compiles its default and reads
 // no environment variable.
 
+// Three run-time bits as compile-time constants: f(c0, c1, c2) with a
+// std::true_type or std::false_type for each bit -- the one place where the
+// launchers' eight template cases (a bit per modality) are spelled out.
+template <class F>
+static auto dispatch3(bool b0, bool b1, bool b2, F f) {
+  auto pick = [](bool b, auto g) {
+    if (b) return g(std::true_type{});
+    return g(std::false_type{});
+  };
+  return pick(b0, [&](auto c0) {
+    return pick(b1, [&](auto c1) { return pick(b2, [&](auto c2) { return f(c0, c1, c2); }); });
+  });
+}
+
 template <bool MM2, int CT, int CA, int CV, int UNR, bool NT, bool NTS, int OCC = 1>
 static void launch_wave_v(const StreamArgs& a, int grid, hipStream_t stream) {
   if (MM2 && a.ids == nullptr && a.emb_dense != a.text_dense) {
@@ -1377,6 +1391,19 @@ static int stream_grid_mult() { return MMB_HOOK_STREAM_GRID_MULT; }
 
 // rows of the column-bound partials (one per wave / workgroup of a launch)
 constexpr int kCmaxRows = 8192;
+
+// The wave kernels' grid: workgroups of 4 waves, a wave per utterance at a
+// time -- ceil(N / 4) of them, at most per_cu per CU of the stream (the
+// resident ones: the rest of the rows by grid stride) and, where the column
+// bounds are taken, at most kCmaxRows / 4 (a partial row per wave: *parts).
+static int wave_grid(const StreamArgs& a, int per_cu, hipStream_t stream, int* parts) {
+  const int64_t blocks = ceil_div(a.N, 4);
+  int grid_cap = per_cu * stream_cu_count(stream);
+  if (a.cmax_part && grid_cap > kCmaxRows / 4) grid_cap = kCmaxRows / 4;
+  const int grid = static_cast<int>(blocks < grid_cap ? blocks : grid_cap);
+  if (parts) *parts = grid * 4;
+  return grid;
+}
 
 // Narrow-frame kernel variant (MMB_STREAM_NARROW, tools build; the product
 // runs 10).  Measured (r03z, MOSI 1M x 20, A = 76, Vd = 48, V = 3016, same
@@ -1404,11 +1431,7 @@ static int launch_narrow(const StreamArgs& a, hipStream_t stream, int* parts) {
   const int var = narrow_variant();
   // resident workgroups of 4 waves per CU at each variant's occupancy
   const int per_cu = (var == 4 || var == 13) ? 2 : var == 5 ? 4 : 3;
-  const int64_t blocks = ceil_div(a.N, 4);
-  int grid_cap = per_cu * stream_cu_count(stream);
-  if (a.cmax_part && grid_cap > kCmaxRows / 4) grid_cap = kCmaxRows / 4;
-  const int grid = static_cast<int>(blocks < grid_cap ? blocks : grid_cap);
-  if (parts) *parts = grid * 4;
+  const int grid = wave_grid(a, per_cu, stream, parts);
 #ifndef MMB_HOOK_NARROW_LAUNCH  // (tools/diag: the variant sweep)
 #define MMB_HOOK_NARROW_LAUNCH false
 #endif
@@ -1420,11 +1443,7 @@ static int launch_narrow(const StreamArgs& a, hipStream_t stream, int* parts) {
 template <bool MM2, int CT, int CA, int CV>
 static int launch_wave(const StreamArgs& a, hipStream_t stream, int* parts = nullptr) {
   if (MM2 && narrow_ok(a) && narrow_variant() > 0) return launch_narrow(a, stream, parts);
-  const int64_t blocks = ceil_div(a.N, 4);
-  int grid_cap = stream_grid_mult() * stream_cu_count(stream);
-  if (a.cmax_part && grid_cap > kCmaxRows / 4) grid_cap = kCmaxRows / 4;
-  const int grid = static_cast<int>(blocks < grid_cap ? blocks : grid_cap);
-  if (parts) *parts = grid * 4;
+  const int grid = wave_grid(a, stream_grid_mult(), stream, parts);
 #ifndef MMB_HOOK_WAVE_LAUNCH  // (tools/diag: the stream-policy sweep)
 #define MMB_HOOK_WAVE_LAUNCH false
 #endif
@@ -2559,31 +2578,19 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
 template <int DIAG, int UNR = 8, int PIPE = 0, int SL = kGSlots, int TM = 7>
 static void launch_fused_v(const FusedArgs& f, int grid, hipStream_t stream) {
   constexpr size_t lds = fused_lds_bytes(SL);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&utt_fused_kernel<UNR, true, DIAG, PIPE, SL, TM>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    attr = true;
-  }
+  allow_dynamic_lds<&utt_fused_kernel<UNR, true, DIAG, PIPE, SL, TM>>(lds);
   utt_fused_kernel<UNR, true, DIAG, PIPE, SL, TM><<<grid, kFThreads, lds, stream>>>(f);
 }
 // the pipelined streamer specialised for the pieces that carry a row tail
 // (a piece-level, wave-uniform choice made here, once per launch)
-static int fused_tail_mask(const FusedArgs& f) {
-  return (f.s.D > 4 * kWave ? 1 : 0) | (f.s.A > 4 * kWave ? 2 : 0) | (f.s.Vd > 4 * kWave ? 4 : 0);
-}
+// (the mask TM: bit 0 text, bit 1 audio, bit 2 visual; asked as "no tail",
+// visual first, so that the kernels are instantiated in the order TM = 0..7)
 template <int UNR, int PIPE>
 static void launch_fused_tm(const FusedArgs& f, int grid, hipStream_t stream) {
-  switch (fused_tail_mask(f)) {
-    case 0: launch_fused_v<0, UNR, PIPE, kGSlots, 0>(f, grid, stream); break;
-    case 1: launch_fused_v<0, UNR, PIPE, kGSlots, 1>(f, grid, stream); break;
-    case 2: launch_fused_v<0, UNR, PIPE, kGSlots, 2>(f, grid, stream); break;
-    case 3: launch_fused_v<0, UNR, PIPE, kGSlots, 3>(f, grid, stream); break;
-    case 4: launch_fused_v<0, UNR, PIPE, kGSlots, 4>(f, grid, stream); break;
-    case 5: launch_fused_v<0, UNR, PIPE, kGSlots, 5>(f, grid, stream); break;
-    case 6: launch_fused_v<0, UNR, PIPE, kGSlots, 6>(f, grid, stream); break;
-    default: launch_fused_v<0, UNR, PIPE, kGSlots, 7>(f, grid, stream); break;
-  }
+  dispatch3(f.s.Vd <= 4 * kWave, f.s.A <= 4 * kWave, f.s.D <= 4 * kWave, [&](auto v, auto a, auto t) {
+    constexpr int TM = (t.value ? 0 : 1) | (a.value ? 0 : 2) | (v.value ? 0 : 4);
+    launch_fused_v<0, UNR, PIPE, kGSlots, TM>(f, grid, stream);
+  });
 }
 // the pipelined streamer's frames per load group (two groups in flight per
 // wave: 20 frames, 100 VGPRs of buffers).  Same-process sweep at 1M rows, T =
@@ -2611,9 +2618,7 @@ static int fused_grid(int64_t nb, hipStream_t stream) {
   return static_cast<int>(std::min<int64_t>(nb, std::min(stream_cu_count(stream), kCmaxRows / 4)));
 }
 
-static int launch_fused(const FusedArgs& f, hipStream_t stream, int* parts) {
-  const int grid = fused_grid(f.nb, stream);
-  if (parts) *parts = grid * 4;
+static int launch_fused(const FusedArgs& f, int grid, hipStream_t stream) {
 #ifndef MMB_HOOK_FUSED_LAUNCH  // (tools/diag: the MMB_FUSED_* sweeps and ablations)
 #define MMB_HOOK_FUSED_LAUNCH false
 #endif
@@ -2659,8 +2664,6 @@ __global__ void calc_weights_kernel(const float* __restrict__ x, int64_t total, 
   }
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int stream_cu_count(hipStream_t stream) {
   int dev = 0, n = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
@@ -2700,6 +2703,75 @@ static int launch_stream(const StreamArgs& a, hipStream_t stream, int* parts = n
     utt_stream_kernel<MM2, VT, VA, VV><<<grid, kNT, 0, stream>>>(a);
   MMB_LAUNCH_CHECK();
   return MMB_OK;
+}
+
+// ------------------------------------------------ the entry points' front end
+// What mmb_sif_wavg and the four MMB2 stream entry points do alike, once:
+// their shared checks and the StreamArgs they hand to a kernel, the empty
+// call, the float4 eligibility of the three modalities, and the column-bound
+// reduction that ends every path.  An entry point keeps what is particular to
+// it: its own limits, its kernel choice and its grid.
+
+// The text source: gathered (ids into table, weights from wtab32 or given
+// per token) or dense (text_dense frames, emb_dense rows, given weights).
+static bool set_text_source(StreamArgs* s, const int32_t* ids, const float* table, int64_t v,
+                            const float* wtab32, const float* text_dense, const float* emb_dense,
+                            const float* w_dense) {
+  if (ids ? !(table && v > 0 && (wtab32 || w_dense)) : !(text_dense && emb_dense && w_dense)) return false;
+  s->ids = ids; s->table = table; s->V = v; s->wtab = wtab32; s->w_dense = w_dense;
+  s->text_dense = text_dense; s->emb_dense = emb_dense;
+  return true;
+}
+
+// The StreamArgs of an MMB2 stream call (s_out is null for the fused kernels,
+// which keep the sums on chip), after the checks every such call gets:
+// positive shapes, the text source, the outputs, bounds only with a workspace.
+static int stream_args(StreamArgs* s, const int32_t* ids, const float* table, int64_t v,
+                       const float* wtab32, const float* text_dense, const float* emb_dense,
+                       const float* w_dense, const float* audio, const float* visual, int64_t n, int t,
+                       int d, int a_, int vd, float* num_out, void* s_out, int s_half, float* aux_out,
+                       int32_t* flag, const uint32_t* colmax, void* colmax_ws) {
+  MMB_REQUIRE(n >= 0 && t > 0 && d > 0 && a_ > 0 && vd > 0);
+  MMB_REQUIRE(audio && visual && num_out && aux_out && (s_half == 0 || s_half == 1));
+  MMB_REQUIRE(colmax == nullptr || colmax_ws != nullptr);
+  *s = StreamArgs{};
+  MMB_REQUIRE(set_text_source(s, ids, table, v, wtab32, text_dense, emb_dense, w_dense));
+  s->audio = audio; s->visual = visual;
+  s->N = n; s->L = t; s->D = d; s->A = a_; s->Vd = vd; s->Kp = mmb_mm2_k(d, a_, vd);
+  s->num_out = num_out; s->s_out = static_cast<float*>(s_out); s->aux_out = aux_out; s->flag = flag;
+  s->s_half = s_half;
+  s->cmax_part = colmax ? static_cast<float*>(colmax_ws) : nullptr;
+  return MMB_OK;
+}
+
+// The empty call: no rows, so every column bound is 0 (cleared by a kernel:
+// no memset node, see zero_words_async).
+static int empty_call(uint32_t* colmax, int d, hipStream_t stream) {
+  return colmax ? zero_words_async(colmax, d, stream) : MMB_OK;
+}
+
+// The end of every path: the column bounds as the max over the `parts`
+// per-wave / per-workgroup rows the stream launch (rc) left in the workspace.
+static int reduce_colmax(int rc, const StreamArgs& s, int parts, uint32_t* colmax, hipStream_t stream) {
+  if (rc != MMB_OK || !colmax) return rc;
+  colmax_reduce_kernel<<<static_cast<unsigned>(ceil_div(s.D, 64)), 1024, 0, stream>>>(s.cmax_part, parts,
+                                                                                      s.D, colmax);
+  MMB_LAUNCH_CHECK();
+  return MMB_OK;
+}
+
+// float4 eligibility of the three modalities: rows of whole float4 units from
+// a 16-byte aligned base
+struct StreamVec {
+  bool t, a, v;
+};
+static StreamVec stream_vec(const StreamArgs& s) {
+  return {s.D % 4 == 0 && (s.ids ? aligned16(s.table) : (aligned16(s.text_dense) && aligned16(s.emb_dense))),
+          s.A % 4 == 0 && aligned16(s.audio), s.Vd % 4 == 0 && aligned16(s.visual)};
+}
+// the workgroup kernels' limit: a thread per column unit (float4 or scalar)
+static bool units_fit(const StreamArgs& s, const StreamVec& vec) {
+  return s.D / (vec.t ? 4 : 1) <= kNT && s.A / (vec.a ? 4 : 1) <= kNT && s.Vd / (vec.v ? 4 : 1) <= kNT;
 }
 
 }  // namespace mmb
@@ -2743,12 +2815,11 @@ extern "C" int mmb_seq2weight(const int32_t* seq, const uint8_t* sel, int64_t n,
 extern "C" int mmb_sif_wavg(const float* table, int64_t v, int d, const int32_t* ids, int64_t n,
                             int l, const float* w, const float* wtab32, float* x_out,
                             float* num_out, float* cnt_out, int32_t* flag, hipStream_t stream) {
-  MMB_REQUIRE(table && ids && v > 0 && d > 0 && n >= 0 && l >= 0);
-  MMB_REQUIRE(w || wtab32);
+  MMB_REQUIRE(ids && d > 0 && n >= 0 && l >= 0);
   MMB_REQUIRE(x_out || num_out || cnt_out);
-  if (n == 0) return MMB_OK;
   StreamArgs a{};
-  a.ids = ids; a.table = table; a.V = v; a.wtab = wtab32; a.w_dense = w;
+  MMB_REQUIRE(set_text_source(&a, ids, table, v, wtab32, nullptr, nullptr, w));
+  if (n == 0) return MMB_OK;
   a.N = n; a.L = l; a.D = d;
   a.x_out = x_out; a.num_out = num_out; a.cnt_out = cnt_out; a.flag = flag;
   const bool v4 = (d % 4 == 0) && aligned16(table);
@@ -2811,69 +2882,30 @@ extern "C" int mmb_mm2_stream(const int32_t* ids, const float* table, int64_t v,
                               float* num_out, void* s_out, int s_half, float* aux_out,
                               int32_t* flag, uint32_t* colmax, void* colmax_ws,
                               hipStream_t stream) {
-  MMB_REQUIRE(n >= 0 && t > 0 && d > 0 && a_ > 0 && vd > 0);
-  MMB_REQUIRE(colmax == nullptr || (colmax_ws != nullptr && d <= 2 * kNT));
-  MMB_REQUIRE(audio && visual && num_out && s_out && aux_out && (s_half == 0 || s_half == 1));
-  if (ids) {
-    MMB_REQUIRE(table && v > 0 && (wtab32 || w_dense));
-  } else {
-    MMB_REQUIRE(text_dense && emb_dense && w_dense);
-  }
-  if (n == 0) {
-    if (colmax) {
-      const hipError_t e = static_cast<hipError_t>(zero_words_async(colmax, static_cast<int64_t>(sizeof(uint32_t) * d) / 4, stream));
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
-    return MMB_OK;
-  }
-  StreamArgs s{};
-  s.cmax_part = colmax ? static_cast<float*>(colmax_ws) : nullptr;
+  StreamArgs s;
+  if (const int rc = stream_args(&s, ids, table, v, wtab32, text_dense, emb_dense, w_dense, audio, visual, n,
+                                 t, d, a_, vd, num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws))
+    return rc;
+  MMB_REQUIRE(s_out && (colmax == nullptr || d <= 2 * kNT));
+  if (n == 0) return empty_call(colmax, d, stream);
   int parts = 0;
-  // the column bounds: max over the launch's per-wave / per-workgroup rows
-  auto reduce_colmax = [&](int rc) {
-    if (rc != MMB_OK || !colmax) return rc;
-    colmax_reduce_kernel<<<static_cast<unsigned>(ceil_div(d, 64)), 1024, 0, stream>>>(
-        static_cast<const float*>(colmax_ws), parts, d, colmax);
-    MMB_LAUNCH_CHECK();
-    return static_cast<int>(MMB_OK);
-  };
-  s.ids = ids; s.table = table; s.V = v; s.wtab = wtab32; s.w_dense = w_dense;
-  s.text_dense = text_dense; s.emb_dense = emb_dense; s.audio = audio; s.visual = visual;
-  s.N = n; s.L = t; s.D = d; s.A = a_; s.Vd = vd; s.Kp = mmb_mm2_k(d, a_, vd);
-  s.num_out = num_out; s.s_out = static_cast<float*>(s_out); s.aux_out = aux_out; s.flag = flag;
-  s.s_half = s_half;
-  const bool vt = (d % 4 == 0) && (ids ? aligned16(table) : (aligned16(text_dense) && aligned16(emb_dense)));
-  const bool va = (a_ % 4 == 0) && aligned16(audio);
-  const bool vv = (vd % 4 == 0) && aligned16(visual);
-  if (vt && va && vv && t <= kWave && d <= 512 && a_ <= 512 && vd <= 512 && aligned16(num_out) &&
+  const StreamVec vec = stream_vec(s);
+  // the wave kernel: float4 rows of every modality and of both outputs, at
+  // most 64 tokens and 512 columns; anything else is not rejected but falls
+  // through to the workgroup kernel
+  if (vec.t && vec.a && vec.v && t <= kWave && d <= 512 && a_ <= 512 && vd <= 512 && aligned16(num_out) &&
       aligned16(s_out)) {
-    const int sel = (d > 256 ? 4 : 0) | (a_ > 256 ? 2 : 0) | (vd > 256 ? 1 : 0);
-    switch (sel) {
-      case 7: return reduce_colmax(launch_wave<true, 2, 2, 2>(s, stream, &parts));
-      case 6: return reduce_colmax(launch_wave<true, 2, 2, 1>(s, stream, &parts));
-      case 5: return reduce_colmax(launch_wave<true, 2, 1, 2>(s, stream, &parts));
-      case 4: return reduce_colmax(launch_wave<true, 2, 1, 1>(s, stream, &parts));
-      case 3: return reduce_colmax(launch_wave<true, 1, 2, 2>(s, stream, &parts));
-      case 2: return reduce_colmax(launch_wave<true, 1, 2, 1>(s, stream, &parts));
-      case 1: return reduce_colmax(launch_wave<true, 1, 1, 2>(s, stream, &parts));
-      default: return reduce_colmax(launch_wave<true, 1, 1, 1>(s, stream, &parts));
-    }
+    const int rc = dispatch3(d > 256, a_ > 256, vd > 256, [&](auto ct, auto ca, auto cv) {
+      return launch_wave<true, ct.value ? 2 : 1, ca.value ? 2 : 1, cv.value ? 2 : 1>(s, stream, &parts);
+    });
+    return reduce_colmax(rc, s, parts, colmax, stream);
   }
-  MMB_REQUIRE(d / (vt ? 4 : 1) <= kNT && a_ / (va ? 4 : 1) <= kNT && vd / (vv ? 4 : 1) <= kNT);
-  s.s_half = 0;
-  const int sel = (vt ? 4 : 0) | (va ? 2 : 0) | (vv ? 1 : 0);
-  int rc;
-  switch (sel) {
-    case 7: rc = launch_stream<true, 4, 4, 4>(s, stream, &parts); break;
-    case 6: rc = launch_stream<true, 4, 4, 1>(s, stream, &parts); break;
-    case 5: rc = launch_stream<true, 4, 1, 4>(s, stream, &parts); break;
-    case 4: rc = launch_stream<true, 4, 1, 1>(s, stream, &parts); break;
-    case 3: rc = launch_stream<true, 1, 4, 4>(s, stream, &parts); break;
-    case 2: rc = launch_stream<true, 1, 4, 1>(s, stream, &parts); break;
-    case 1: rc = launch_stream<true, 1, 1, 4>(s, stream, &parts); break;
-    default: rc = launch_stream<true, 1, 1, 1>(s, stream, &parts); break;
-  }
-  rc = reduce_colmax(rc);
+  MMB_REQUIRE(units_fit(s, vec));
+  s.s_half = 0;  // fp32 sums; split_rows_kernel makes them fp16 hi | lo afterwards
+  int rc = dispatch3(vec.t, vec.a, vec.v, [&](auto vt, auto va, auto vv) {
+    return launch_stream<true, vt.value ? 4 : 1, va.value ? 4 : 1, vv.value ? 4 : 1>(s, stream, &parts);
+  });
+  rc = reduce_colmax(rc, s, parts, colmax, stream);
   if (rc != MMB_OK || !s_half) return rc;
   split_rows_kernel<<<static_cast<unsigned>(n), 256, s.Kp * sizeof(float), stream>>>(
       s.s_out, aux_out + 2 * n, s.Kp);
@@ -2934,54 +2966,27 @@ extern "C" int mmb_mm2_stream_split(const int32_t* ids, const float* table, int6
                                     float* num_out, void* s_out, int s_half, float* aux_out,
                                     int32_t* flag, uint32_t* colmax, void* colmax_ws, int parts,
                                     void* ws, size_t ws_bytes, hipStream_t stream) {
-  MMB_REQUIRE(n >= 0 && t > 0 && d > 0 && a_ > 0 && vd > 0 && parts >= 0);
-  MMB_REQUIRE(colmax == nullptr || (colmax_ws != nullptr && d <= 2 * kNT && n <= kCmaxRows));
-  MMB_REQUIRE(audio && visual && num_out && s_out && aux_out && (s_half == 0 || s_half == 1));
-  if (ids) {
-    MMB_REQUIRE(table && v > 0 && (wtab32 || w_dense));
-  } else {
-    MMB_REQUIRE(text_dense && emb_dense && w_dense);
-  }
-  if (n == 0) {
-    if (colmax) {
-      const hipError_t e = static_cast<hipError_t>(zero_words_async(colmax, d, stream));
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
-    return MMB_OK;
-  }
+  StreamArgs s;
+  if (const int rc = stream_args(&s, ids, table, v, wtab32, text_dense, emb_dense, w_dense, audio, visual, n,
+                                 t, d, a_, vd, num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws))
+    return rc;
+  // the bounds: a partial row per utterance
+  MMB_REQUIRE(s_out && parts >= 0 && (colmax == nullptr || (d <= 2 * kNT && n <= kCmaxRows)));
+  // the empty call returns before the workspace is looked at, and before
+  // mmb_mm2_stream_split_parts queries the device
+  if (n == 0) return empty_call(colmax, d, stream);
   const int P = parts > 0 ? std::min(parts, t) : mmb_mm2_stream_split_parts(n, t);
   const SplitPlan q = split_plan_of(t, d, a_, vd, P, parts > 0 ? 1 : kSplitTextX);
   MMB_REQUIRE(ws && ws_bytes >= split_ws_floats(n, q) * sizeof(float));
   MMB_REQUIRE(n * (q.Pt + 2 * q.Pf) <= (int64_t{1} << 31) - 1);
   MMB_REQUIRE(3 * d + 2 * a_ + 2 * vd <= kSplitJ * kNT);  // the finish kernel's columns
-  StreamArgs s{};
-  s.cmax_part = colmax ? static_cast<float*>(colmax_ws) : nullptr;
-  s.ids = ids; s.table = table; s.V = v; s.wtab = wtab32; s.w_dense = w_dense;
-  s.text_dense = text_dense; s.emb_dense = emb_dense; s.audio = audio; s.visual = visual;
-  s.N = n; s.L = t; s.D = d; s.A = a_; s.Vd = vd; s.Kp = mmb_mm2_k(d, a_, vd);
-  s.num_out = num_out; s.s_out = static_cast<float*>(s_out); s.aux_out = aux_out; s.flag = flag;
-  s.s_half = s_half;
-  const bool vt = (d % 4 == 0) && (ids ? aligned16(table) : (aligned16(text_dense) && aligned16(emb_dense)));
-  const bool va = (a_ % 4 == 0) && aligned16(audio);
-  const bool vv = (vd % 4 == 0) && aligned16(visual);
-  MMB_REQUIRE(d / (vt ? 4 : 1) <= kNT && a_ / (va ? 4 : 1) <= kNT && vd / (vv ? 4 : 1) <= kNT);
-  float* part = static_cast<float*>(ws);
-  int rc;
-  switch ((vt ? 4 : 0) | (va ? 2 : 0) | (vv ? 1 : 0)) {
-    case 7: rc = launch_split<4, 4, 4>(s, q, part, stream); break;
-    case 6: rc = launch_split<4, 4, 1>(s, q, part, stream); break;
-    case 5: rc = launch_split<4, 1, 4>(s, q, part, stream); break;
-    case 4: rc = launch_split<4, 1, 1>(s, q, part, stream); break;
-    case 3: rc = launch_split<1, 4, 4>(s, q, part, stream); break;
-    case 2: rc = launch_split<1, 4, 1>(s, q, part, stream); break;
-    case 1: rc = launch_split<1, 1, 4>(s, q, part, stream); break;
-    default: rc = launch_split<1, 1, 1>(s, q, part, stream); break;
-  }
-  if (rc != MMB_OK || !colmax) return rc;
-  colmax_reduce_kernel<<<static_cast<unsigned>(ceil_div(d, 64)), 1024, 0, stream>>>(
-      static_cast<const float*>(colmax_ws), static_cast<int>(n), d, colmax);
-  MMB_LAUNCH_CHECK();
-  return MMB_OK;
+  const StreamVec vec = stream_vec(s);
+  MMB_REQUIRE(units_fit(s, vec));
+  const int rc = dispatch3(vec.t, vec.a, vec.v, [&](auto vt, auto va, auto vv) {
+    return launch_split<vt.value ? 4 : 1, va.value ? 4 : 1, vv.value ? 4 : 1>(s, q, static_cast<float*>(ws),
+                                                                             stream);
+  });
+  return reduce_colmax(rc, s, static_cast<int>(n), colmax, stream);
 }
 
 extern "C" int mmb_mm2_stream_project_supported(int t, int d, int a_, int vd) {
@@ -2998,40 +3003,26 @@ extern "C" int mmb_mm2_stream_project(const int32_t* ids, const float* table, in
                                       const float* c0, float* num_out, float* aux_out,
                                       float* mmb2_out, int32_t* flag, uint32_t* colmax,
                                       void* colmax_ws, hipStream_t stream) {
-  MMB_REQUIRE(n >= 0 && mmb_mm2_stream_project_supported(t, d, a_, vd));
-  MMB_REQUIRE(audio && visual && num_out && aux_out && mmb2_out && wpieces && c0);
-  MMB_REQUIRE(colmax == nullptr || colmax_ws != nullptr);
-  if (ids) {
-    MMB_REQUIRE(table && v > 0 && (wtab32 || w_dense) && aligned16(table));
-  } else {
-    MMB_REQUIRE(text_dense && w_dense && aligned16(text_dense));
-  }
-  MMB_REQUIRE(aligned16(audio) && aligned16(visual) && aligned16(num_out) && aligned16(wpieces));
-  if (n == 0) {
-    if (colmax) {
-      const hipError_t e = static_cast<hipError_t>(zero_words_async(colmax, static_cast<int64_t>(sizeof(uint32_t) * d) / 4, stream));
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
-    return MMB_OK;
-  }
   FusedArgs f{};
-  StreamArgs& s = f.s;
-  s.ids = ids; s.table = table; s.V = v; s.wtab = wtab32; s.w_dense = w_dense;
-  s.text_dense = text_dense; s.emb_dense = text_dense; s.audio = audio; s.visual = visual;
-  s.N = n; s.L = t; s.D = d; s.A = a_; s.Vd = vd; s.Kp = mmb_mm2_k(d, a_, vd);
-  s.num_out = num_out; s.aux_out = aux_out; s.flag = flag; s.s_half = 1;
-  s.cmax_part = colmax ? static_cast<float*>(colmax_ws) : nullptr;
-  const int w3[3] = {d, a_, vd};
-  int kq = 0;
-  for (int m = 0; m < 3; ++m) {
-    f.kq[m] = (2 * w3[m] + 31) / 32 * 32;
-    kq += f.kq[m];
-  }
+  // the weighted sum's rows are the text frames themselves; the sums stay on
+  // chip (no s_out), fp16 hi | lo
+  if (const int rc = stream_args(&f.s, ids, table, v, wtab32, text_dense, text_dense, w_dense, audio, visual, n,
+                                 t, d, a_, vd, num_out, nullptr, 1, aux_out, flag, colmax, colmax_ws))
+    return rc;
+  MMB_REQUIRE(mmb_mm2_stream_project_supported(t, d, a_, vd) && mmb2_out && wpieces && c0);
+  // float4 rows are required here, not an option: no scalar fused kernel
+  const StreamVec vec = stream_vec(f.s);
+  MMB_REQUIRE(vec.t && vec.a && vec.v && aligned16(num_out) && aligned16(wpieces));
+  if (n == 0) return empty_call(colmax, d, stream);
+  f.kq[0] = piece_k(d);
+  f.kq[1] = piece_k(a_);
+  f.kq[2] = piece_k(vd);
   f.img = static_cast<const _Float16*>(wpieces);
-  f.col_inv = reinterpret_cast<const float*>(f.img + 2 * static_cast<size_t>(kFLdw) * kq);
+  f.col_inv = reinterpret_cast<const float*>(f.img + 2 * static_cast<size_t>(kFLdw) * (f.kq[0] + f.kq[1] + f.kq[2]));
   f.c0 = c0;
   f.out = mmb2_out;
   f.nb = ceil_div(n, kGR);
+  const int grid = fused_grid(f.nb, stream);
   f.balanced = 1;  // balanced tail: 22.35 -> 22.26 ms (r02s)
   // the dynamic batch schedule's counter, past the column-bound partials
   // (zeroed here by a kernel: no memset node in a captured step)
@@ -3041,29 +3032,21 @@ extern "C" int mmb_mm2_stream_project(const int32_t* ids, const float* table, in
 #ifdef MMB_HOOK_FUSED_ARGS  // (tools/diag: MMB_FUSED_BALANCED / MMB_FUSED_DYN)
   MMB_HOOK_FUSED_ARGS(f);
 #endif
-  {
-    // the dynamic order from 16 rounds of batches on (fewer: the static round
-    // robin, whose finishing times spread little there); its units: 48-row
-    // batches, then the last ~G batches' rows as 12-row units.  Same-process
-    // A/B (tools/fused_dyn_ab.py, r05af/ag, fused kernel ms static ->
-    // dynamic): 1M 22.63 -> 22.38, 500k 11.41 -> 11.28, 250k 5.98 -> 5.96;
-    // 125k (10 rounds) 2.98 -> 3.06, so it stays static
-    const int64_t G = fused_grid(f.nb, stream);
-    if (f.nb < 16 * G) f.sched = nullptr;
-    if (f.sched) {
-      f.big = std::max<int64_t>(0, n - kGR * G) / kGR;
-      f.nu = f.big + ceil_div(n - f.big * kGR, kGR / 4);
-      const hipError_t e = static_cast<hipError_t>(zero_words_async(f.sched, 1, stream));
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
+  // the dynamic order from 16 rounds of batches on (fewer: the static round
+  // robin, whose finishing times spread little there); its units: 48-row
+  // batches, then the last ~G batches' rows as 12-row units.  Same-process
+  // A/B (tools/fused_dyn_ab.py, r05af/ag, fused kernel ms static ->
+  // dynamic): 1M 22.63 -> 22.38, 500k 11.41 -> 11.28, 250k 5.98 -> 5.96;
+  // 125k (10 rounds) 2.98 -> 3.06, so it stays static
+  const int64_t G = grid;
+  if (f.nb < 16 * G) f.sched = nullptr;
+  if (f.sched) {
+    f.big = std::max<int64_t>(0, n - kGR * G) / kGR;
+    f.nu = f.big + ceil_div(n - f.big * kGR, kGR / 4);
+    if (const int rc = zero_words_async(f.sched, 1, stream)) return rc;
   }
-  int parts = 0;
-  const int rc = launch_fused(f, stream, &parts);
-  if (rc != MMB_OK || !colmax) return rc;
-  colmax_reduce_kernel<<<static_cast<unsigned>(ceil_div(d, 64)), 1024, 0, stream>>>(
-      static_cast<const float*>(colmax_ws), parts, d, colmax);
-  MMB_LAUNCH_CHECK();
-  return MMB_OK;
+  // the bounds: a partial row per streamer wave
+  return reduce_colmax(launch_fused(f, grid, stream), f.s, grid * 4, colmax, stream);
 }
 
 
@@ -3615,7 +3598,7 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
 }  // namespace mmb
 
 extern "C" int mmb_mm2_stream_project_narrow_supported(int t, int d, int a_, int vd, int64_t v) {
-  const int kq = (2 * a_ + 31) / 32 * 32 + (2 * vd + 31) / 32 * 32;
+  const int kq = piece_k(a_) + piece_k(vd);
   return t > 0 && t <= kWave && d > 256 && d < kNFLdp && d % 4 == 0 && a_ >= 4 && vd >= 4 &&
          a_ <= 128 && vd <= 128 && a_ % 4 == 0 && vd % 4 == 0 && kq <= kNFK && v > 0 && v <= 16384 &&
          v * (kNFLdq + 2) * 4 + 4 * kNFHot < (int64_t{1} << 31) && static_cast<int64_t>(t) * (a_ > vd ? a_ : vd) * 4 < (int64_t{1} << 31);
@@ -3628,32 +3611,25 @@ extern "C" int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* ta
                                              const float* c0, float* num_out, float* aux_out,
                                              float* mmb2_out, int32_t* flag, uint32_t* colmax,
                                              void* colmax_ws, hipStream_t stream) {
-  MMB_REQUIRE(n >= 0 && n < (int64_t{1} << 31) - kNFRows && mmb_mm2_stream_project_narrow_supported(t, d, a_, vd, v));
-  MMB_REQUIRE(ids && table && wtab32 && text_cache && audio && visual && num_out && aux_out &&
-              mmb2_out && wpieces && c0);
-  MMB_REQUIRE(colmax == nullptr || colmax_ws != nullptr);
-  MMB_REQUIRE(aligned16(table) && aligned16(text_cache) && aligned16(audio) && aligned16(visual) &&
-              aligned16(num_out) && aligned16(mmb2_out) && aligned16(wpieces));
-  if (n == 0) {
-    if (colmax) {
-      const hipError_t e = static_cast<hipError_t>(zero_words_async(colmax, static_cast<int64_t>(sizeof(uint32_t) * d) / 4, stream));
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
-    return MMB_OK;
-  }
   NarrowFusedArgs f{};
-  StreamArgs& s = f.s;
-  s.ids = ids; s.table = table; s.V = v; s.wtab = wtab32; s.audio = audio; s.visual = visual;
-  s.N = n; s.L = t; s.D = d; s.A = a_; s.Vd = vd; s.Kp = mmb_mm2_k(d, a_, vd);
-  s.num_out = num_out; s.aux_out = aux_out; s.flag = flag; s.s_half = 1;
-  s.cmax_part = colmax ? static_cast<float*>(colmax_ws) : nullptr;
+  // gathered text with the weight table only; the sums stay on chip
+  MMB_REQUIRE(ids && wtab32);
+  if (const int rc = stream_args(&f.s, ids, table, v, wtab32, nullptr, nullptr, nullptr, audio, visual, n, t, d,
+                                 a_, vd, num_out, nullptr, 1, aux_out, flag, colmax, colmax_ws))
+    return rc;
+  MMB_REQUIRE(n < (int64_t{1} << 31) - kNFRows && mmb_mm2_stream_project_narrow_supported(t, d, a_, vd, v));
+  MMB_REQUIRE(text_cache && mmb2_out && wpieces && c0);
+  const StreamVec vec = stream_vec(f.s);
+  MMB_REQUIRE(vec.t && vec.a && vec.v && aligned16(text_cache) && aligned16(num_out) && aligned16(mmb2_out) &&
+              aligned16(wpieces));
+  if (n == 0) return empty_call(colmax, d, stream);
   f.ptab = static_cast<const float*>(text_cache);
   f.hot_slot1 = reinterpret_cast<const int32_t*>(f.ptab + static_cast<size_t>(v) * kNFLdq);
   f.hot_ids = f.hot_slot1 + v;
   f.n_hot = static_cast<int>(v < kNFHot ? v : kNFHot);
-  const int kq_t = (2 * d + 31) / 32 * 32;
-  f.kq_a = (2 * a_ + 31) / 32 * 32;
-  f.kq_v = (2 * vd + 31) / 32 * 32;
+  const int kq_t = piece_k(d);
+  f.kq_a = piece_k(a_);
+  f.kq_v = piece_k(vd);
   f.cb_av = kq_t / 32;
   f.img = static_cast<const _Float16*>(wpieces);
   f.col_inv = reinterpret_cast<const float*>(f.img + 2 * static_cast<size_t>(kNFLdw) * (kq_t + f.kq_a + f.kq_v));
@@ -3671,16 +3647,12 @@ extern "C" int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* ta
   f.team_lag = teams == 2 ? 1 : 0;
   // batches: of 8 rpw rows, or of 4 rpw rows per team (two per workgroup)
   f.nb = ceil_div(n, static_cast<int64_t>(teams ? kNFWaves / 2 : kNFWaves) * f.rpw);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kNFLds));
+  allow_dynamic_lds<&utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV>>(kNFLds);
 #ifdef MMB_HOOK_NF_TEAMS_ATTR
-    MMB_HOOK_NF_TEAMS_ATTR;
+  MMB_HOOK_NF_TEAMS_ATTR;
 #endif
-    attr = true;
-  }
-  int64_t grid = stream_cu_count(stream);
+  // one workgroup per CU; the bounds: a partial row per wave
+  int64_t grid = cus;
   if (colmax && grid > kCmaxRows / kNFWaves) grid = kCmaxRows / kNFWaves;
   if (grid > (teams ? ceil_div(f.nb, int64_t{2}) : f.nb)) grid = teams ? ceil_div(f.nb, int64_t{2}) : f.nb;
 #ifndef MMB_HOOK_NF_TEAMS_LAUNCH
@@ -3689,11 +3661,7 @@ extern "C" int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* ta
   if (!(MMB_HOOK_NF_TEAMS_LAUNCH))
     utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV><<<static_cast<unsigned>(grid), kNFThreads, kNFLds, stream>>>(f);
   MMB_LAUNCH_CHECK();
-  if (!colmax) return MMB_OK;
-  colmax_reduce_kernel<<<static_cast<unsigned>(ceil_div(d, 64)), 1024, 0, stream>>>(
-      static_cast<const float*>(colmax_ws), static_cast<int>(grid) * kNFWaves, d, colmax);
-  MMB_LAUNCH_CHECK();
-  return MMB_OK;
+  return reduce_colmax(MMB_OK, f.s, static_cast<int>(grid) * kNFWaves, colmax, stream);
 }
 
 // the tools build's variant launches, knobs and probes (tools/diag/); the

@@ -569,14 +569,8 @@ def mm2_stream_project_narrow(n, t, d, a, vd, audio, visual, proj: "MMB2Projecti
                               table, wtab32, flag=None, out=None, colmax=None, colmax_ws=None):
     """a1-a8 at narrow frame widths in ONE kernel (mmb_mm2_stream_project_narrow):
     x, aux, the MMB2 rows (and the column bounds).  Returns (x, aux, mmb2)."""
-    dev = audio.device
-    if out is None:
-        out = (torch.empty((n, d), dtype=torch.float32, device=dev),
-               torch.empty((3, n), dtype=torch.float32, device=dev),
-               torch.empty((n, d), dtype=torch.float32, device=dev))
-    num, aux, mmb2 = out
     proj.enable_text_cache(table, wtab32)
-    _check_colmax_ws(colmax_ws, d)
+    num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
     L.call("mmb_mm2_stream_project_narrow", L.ptr(ids32), L.ptr(table), table.shape[0],
            L.ptr(wtab32), L.ptr(proj.text_cache), L.ptr(audio), L.ptr(visual), n, t, d, a, vd,
            L.ptr(proj.wpieces), L.ptr(proj.c0), L.ptr(num), L.ptr(aux), L.ptr(mmb2), L.ptr(flag),
@@ -590,20 +584,25 @@ def mm2_stream_project(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", id
     """a6-a8 in ONE kernel (mmb_mm2_stream_project): x, aux (and the column
     bounds) as mm2_stream, plus the MMB2 rows of mm2_project -- the sums s
     stay in LDS.  Returns (x, aux, mmb2)."""
-    dev = audio.device
-    if out is None:
-        out = (torch.empty((n, d), dtype=torch.float32, device=dev),
-               torch.empty((3, n), dtype=torch.float32, device=dev),
-               torch.empty((n, d), dtype=torch.float32, device=dev))
-    num, aux, mmb2 = out
     proj.enable_pieces()
+    num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
     V = table.shape[0] if table is not None else 0
-    _check_colmax_ws(colmax_ws, d)
     L.call("mmb_mm2_stream_project", L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32),
            L.ptr(text_dense), L.ptr(w_dense), L.ptr(audio), L.ptr(visual), n, t, d, a, vd,
            L.ptr(proj.wpieces), L.ptr(proj.c0), L.ptr(num), L.ptr(aux), L.ptr(mmb2), L.ptr(flag),
            L.ptr(colmax), L.ptr(colmax_ws), L.stream_ptr())
     return num, aux, mmb2
+
+
+def _fused_outputs(n: int, d: int, device, out, colmax_ws):
+    """(x, aux, mmb2) of the fused wrappers -- `out` if given, else allocated
+    -- after the workspace's size check."""
+    _check_colmax_ws(colmax_ws, d)
+    if out is None:
+        out = (torch.empty((n, d), dtype=torch.float32, device=device),
+               torch.empty((3, n), dtype=torch.float32, device=device),
+               torch.empty((n, d), dtype=torch.float32, device=device))
+    return out
 
 
 def _check_colmax_ws(colmax_ws, d: int) -> None:

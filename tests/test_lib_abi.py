@@ -112,6 +112,118 @@ def test_invalid_arguments_rejected_without_gpu():
         mmb_lib.call("mmb_host_randn", 0, -1, None)
 
 
+# ---- the same for the stream and x3 projection entry points, as a table: ----
+# ---- argument checks and empty calls that return before any device call  ----
+# Stand-ins for device pointers: 16-byte aligned, never dereferenced (every
+# row below returns before a launch or a device query).
+P = 0x7F0000001000
+KCMAX_ROWS = 8192  # rows of the column-bound workspace (mmb_mm2_colmax_ws_bytes(d) // (4 d))
+
+STREAM = ("ids table v wtab32 text_dense emb_dense w_dense audio visual n t d a vd num_out s_out "
+          "s_half aux_out flag colmax colmax_ws").split()
+ENTRY_ARGS = {
+    "mmb_sif_wavg": "table v d ids n l w wtab32 x_out num_out cnt_out flag stream".split(),
+    "mmb_mm2_stream": STREAM + ["stream"],
+    "mmb_mm2_stream_split": STREAM + "parts ws ws_bytes stream".split(),
+    "mmb_mm2_stream_project": ("ids table v wtab32 text_dense w_dense audio visual n t d a vd wpieces c0 "
+                               "num_out aux_out mmb2_out flag colmax colmax_ws stream").split(),
+    "mmb_mm2_stream_project_narrow": ("ids table v wtab32 text_cache audio visual n t d a vd wpieces c0 "
+                                      "num_out aux_out mmb2_out flag colmax colmax_ws stream").split(),
+    "mmb_mm2_project_x3": "s_split num aux wsplit ldw c0 n k d out stream".split(),
+    "mmb_mm2_project_x3_rmpc": "s_split num aux wsplit ldw c0 n k d out pc sif_out stream".split(),
+    "mmb_mm2_project_x3_split": ("s_split num aux wsplit ldw c0 n k d out pc sif_out slices ws ws_bytes "
+                                 "stream").split(),
+}
+# a valid gathered-text call of each kind (n > 0: it would go on to launch)
+GATHER = dict(ids=P, table=P, v=1000, wtab32=P, text_dense=None, emb_dense=None, w_dense=None, audio=P,
+              visual=P, n=100, t=40, d=300, a=300, vd=300, num_out=P, s_out=P, s_half=1, aux_out=P,
+              flag=None, colmax=None, colmax_ws=None, stream=None)
+BASE = {
+    "mmb_sif_wavg": dict(table=P, v=1000, d=300, ids=P, n=100, l=40, w=None, wtab32=P, x_out=P,
+                         num_out=None, cnt_out=None, flag=None, stream=None),
+    "mmb_mm2_stream": GATHER,
+    # parts > 0: parts = 0 asks the device for its CU count
+    "mmb_mm2_stream_split": dict(GATHER, parts=2, ws=P, ws_bytes=1 << 40),
+    "mmb_mm2_stream_project": dict(GATHER, wpieces=P, c0=P, mmb2_out=P),
+    "mmb_mm2_stream_project_narrow": dict(GATHER, v=3016, t=20, a=76, vd=48, text_cache=P, wpieces=P, c0=P,
+                                          mmb2_out=P),
+}
+X3 = dict(s_split=P, num=P, aux=P, wsplit=P, ldw=320, c0=P, n=100, k=1824, d=300, out=P, pc=None,
+          sif_out=None, slices=2, ws=P, ws_bytes=1 << 40, stream=None)  # slices = 0 asks the device
+for _name in ("mmb_mm2_project_x3", "mmb_mm2_project_x3_rmpc", "mmb_mm2_project_x3_split"):
+    BASE[_name] = X3
+DENSE = dict(ids=None, table=None, v=0, wtab32=None, text_dense=P, emb_dense=P, w_dense=P)
+BOUNDS = dict(colmax=P, colmax_ws=P)
+EINVAL, OK = -1, 0
+
+
+def _split_ws_bytes(**kw):
+    a = dict(GATHER, parts=2, **kw)
+    return mmb_lib.query("mmb_mm2_stream_split_ws_bytes", a["n"], a["t"], a["d"], a["a"], a["vd"], a["parts"])
+
+
+CASES = [
+    ("mmb_mm2_stream", "scalar D 321", dict(d=321), EINVAL),
+    ("mmb_mm2_stream", "scalar A 321", dict(a=321), EINVAL),
+    ("mmb_mm2_stream", "scalar Vd 321", dict(vd=321), EINVAL),
+    ("mmb_mm2_stream", "bounds without workspace", dict(colmax=P), EINVAL),
+    ("mmb_mm2_stream", "bounds at D 644", dict(BOUNDS, d=644), EINVAL),
+    ("mmb_mm2_stream", "ids without table", dict(table=None), EINVAL),
+    ("mmb_mm2_stream", "dense text without emb_dense", dict(DENSE, emb_dense=None), EINVAL),
+    ("mmb_mm2_stream", "s_half 2", dict(s_half=2), EINVAL),
+    ("mmb_mm2_stream_split", "bounds with n past the workspace rows", dict(BOUNDS, n=KCMAX_ROWS + 1), EINVAL),
+    ("mmb_mm2_stream_split", "workspace one byte short", lambda: dict(ws_bytes=_split_ws_bytes() - 1), EINVAL),
+    ("mmb_mm2_stream_split", "past the finish kernel's columns", dict(d=512), EINVAL),
+    ("mmb_mm2_stream_split", "parts -1", dict(parts=-1), EINVAL),
+    ("mmb_mm2_stream_project", "audio misaligned by 4 bytes", dict(audio=P + 4), EINVAL),
+    ("mmb_mm2_stream_project", "D 252", dict(d=252), EINVAL),
+    ("mmb_mm2_stream_project", "D 320", dict(d=320), EINVAL),
+    ("mmb_mm2_stream_project", "A 322", dict(a=322), EINVAL),
+    ("mmb_mm2_stream_project", "missing wpieces", dict(wpieces=None), EINVAL),
+    ("mmb_mm2_stream_project_narrow", "V 16385", dict(v=16385), EINVAL),
+    ("mmb_mm2_stream_project_narrow", "A 132", dict(a=132), EINVAL),
+    ("mmb_mm2_stream_project_narrow", "D 256", dict(d=256), EINVAL),
+    ("mmb_mm2_stream_project_narrow", "missing text_cache", dict(text_cache=None), EINVAL),
+]
+for _name in ("mmb_mm2_project_x3", "mmb_mm2_project_x3_rmpc", "mmb_mm2_project_x3_split"):
+    CASES += [(_name, "k 100", dict(k=100), EINVAL),
+              (_name, "ldw 384", dict(ldw=384), EINVAL),
+              (_name, "misaligned s_split", dict(s_split=P + 8), EINVAL)]
+    if _name != "mmb_mm2_project_x3":
+        CASES.append((_name, "pc without sif_out", dict(pc=P), EINVAL))
+# the empty call without bounds: MMB_OK, nothing enqueued (the split one before
+# its workspace is looked at or its plan asks the device)
+CASES += [(name, "n 0", dict(n=0), OK) for name in ("mmb_sif_wavg", "mmb_mm2_stream", "mmb_mm2_stream_project",
+                                                    "mmb_mm2_stream_project_narrow")]
+CASES.append(("mmb_mm2_stream_split", "n 0, no workspace", dict(n=0, parts=0, ws=None, ws_bytes=0), OK))
+
+
+def test_case_table_starts_from_valid_calls():
+    """Every rejection row changes one thing of a call the library's own
+    shape queries accept, so the rejection is the row's and not the base's."""
+    g = GATHER
+    assert mmb_lib.query("mmb_mm2_stream_project_supported", g["t"], g["d"], g["a"], g["vd"])
+    nf = BASE["mmb_mm2_stream_project_narrow"]
+    assert mmb_lib.query("mmb_mm2_stream_project_narrow_supported", nf["t"], nf["d"], nf["a"], nf["vd"], nf["v"])
+    assert X3["ldw"] == mmb_lib.query("mmb_mm2_ldw", X3["d"])
+    assert X3["k"] == mmb_lib.query("mmb_mm2_k", X3["d"], 300, 300)
+    assert mmb_lib.query("mmb_mm2_colmax_ws_bytes", g["d"]) // (4 * g["d"]) == KCMAX_ROWS
+    assert 0 < _split_ws_bytes() < BASE["mmb_mm2_stream_split"]["ws_bytes"]
+    assert 0 < _split_ws_bytes(d=512) < BASE["mmb_mm2_stream_split"]["ws_bytes"]
+
+
+@pytest.mark.parametrize("name,what,change,want", CASES, ids=[f"{c[0]}-{c[1]}".replace(" ", "_") for c in CASES])
+def test_invalid_arguments_rejected_without_gpu_table(name, what, change, want):
+    # argument validation, and the empty call, happen before any launch
+    filled = dict(BASE[name], **(change() if callable(change) else change))
+    args = [filled[k] for k in ENTRY_ARGS[name]]
+    if want == OK:
+        assert mmb_lib.call(name, *args) == 0
+    else:
+        with pytest.raises(mmb_lib.MMBError, match=r"code -1 \(invalid argument\)"):
+            mmb_lib.call(name, *args)
+
+
 def test_environment_cannot_redirect_the_product_library(tmp_path):
     """MMB_LIB_PATH (the round-3 A/B hook) no longer exists: a fresh process
     with it set to the tools build still loads libmmb.so; the tools build is

@@ -134,8 +134,7 @@ bool diag_stream_small(const A& a, int grid, hipStream_t stream) {
 // attribute and launch
 template <int I>
 void diag_nf_teams_attr() {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kNFLds));
+  allow_dynamic_lds<&utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV, true>>(kNFLds);
 }
 template <class F>
 bool diag_nf_teams_launch(int teams, const F& f, int64_t grid, hipStream_t stream) {
