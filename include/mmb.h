@@ -256,6 +256,36 @@ int mmb_mm2_stream(const int32_t* ids, const float* table, int64_t v, const floa
                    int vd, float* num_out, void* s_out, int s_half, float* aux_out,
                    int32_t* flag, uint32_t* colmax, void* colmax_ws, hipStream_t stream);
 
+/* mmb_mm2_stream on audio / visual frames kept in 16-bit storage.  Text is
+ * gathered (ids + table, weights from wtab32 or per token from w_dense); both
+ * frame tensors, [n,t,a] and [n,t,vd] contiguous, hold elements of
+ * frame_type.  A frame value is widened to f32 in registers right after its
+ * (non-temporal) load -- exact for both 16-bit types, fp16 subnormals
+ * included -- and summed by the statements of mmb_mm2_stream in their order:
+ * every output is bit for bit what mmb_mm2_stream writes for the same frames
+ * upcast to f32 by the caller (where that call takes the same kernel: the
+ * 16-bit types never take its narrow-frame route).  The library rounds
+ * nothing: the caller chose the 16-bit values.  Outputs, layouts, the empty
+ * call and the flag bits are mmb_mm2_stream's.
+ * MMB_FRAMES_F32 is mmb_mm2_stream itself for the same arguments.
+ * 16-bit frames: the wave kernel at t <= 64, widths % 4 == 0 and <= 512,
+ * table / num_out / s_out 16-byte and audio / visual 8-byte aligned (a
+ * column unit is 4 values = one 8-byte load); otherwise the workgroup kernel,
+ * a modality in 4-value units when its width % 4 == 0 and its base is 8-byte
+ * aligned (up to 1280 wide), in scalar 2-byte loads if not (up to 320).
+ * MMB_EINVAL before any launch: a frame_type outside 0..2, a 16-bit frame
+ * base that is not 2-byte aligned, anything mmb_mm2_stream rejects.
+ * replaces the frame loops of sif2.estimate_embedding_overall_gpu2
+ *   /root/reference/sif2.py:181-205 (which reads f32 frames only)            */
+#define MMB_FRAMES_F32 0
+#define MMB_FRAMES_F16 1 /* IEEE binary16 */
+#define MMB_FRAMES_BF16 2
+int mmb_mm2_stream_ft(const int32_t* ids, const float* table, int64_t v, const float* wtab32,
+                      const float* w_dense, const void* audio, const void* visual, int frame_type,
+                      int64_t n, int t, int d, int a, int vd, float* num_out, void* s_out,
+                      int s_half, float* aux_out, int32_t* flag, uint32_t* colmax,
+                      void* colmax_ws, hipStream_t stream);
+
 /* mmb_mm2_stream for a few long rows (POM's splits: 100 / 203 transcripts of
  * 1089 / 1357 tokens), split over workgroups: every utterance is cut into P
  * token / frame ranges (parts = 0: mmb_mm2_stream_split_parts, about one

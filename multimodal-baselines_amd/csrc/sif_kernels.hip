@@ -30,8 +30,8 @@ struct StreamArgs {
   const float* w_dense;     // [N,L] given weights
   const float* text_dense;  // [N,L,D] dense text frames (MMB2 drop-in mode)
   const float* emb_dense;   // [N,L,D] rows for the weighted sum (may alias text_dense)
-  const float* audio;       // [N,L,A]
-  const float* visual;      // [N,L,Vd]
+  const float* audio;       // [N,L,A]   (elements of the kernel's frame type FE: a 16-bit
+  const float* visual;      // [N,L,Vd]   instantiation reads both through const FE*)
   int64_t N;
   int L, D, A, Vd, Kp;
   float* x_out;
@@ -65,10 +65,48 @@ __device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
     v[0] = *p;
   }
 }
-// the same, non-temporal: for the read-once frame streams
-template <int VEC>
-__device__ __forceinline__ void ldv_nt(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
+// Frame element types of the MMB2 stream kernels (mmb_mm2_stream_ft): f32, or
+// 16-bit storage widened to f32 in registers right after the load.  Both
+// widenings are exact (fp16 subnormals included), so a kernel instantiated
+// for a 16-bit type sums what its f32 instantiation sums on the upcast
+// frames, bit for bit.
+using f16_t = _Float16;  // IEEE binary16
+struct bf16_t {          // bfloat16: the high half of an f32
+  uint16_t bits;
+};
+using u2 = unsigned __attribute__((ext_vector_type(2)));  // four 16-bit frame values
+template <class FE>
+__device__ __forceinline__ float frame_f32(uint32_t bits16) {
+  if constexpr (std::is_same_v<FE, bf16_t>) {
+    return __uint_as_float(bits16 << 16);
+  } else {
+    return static_cast<float>(__builtin_bit_cast(f16_t, static_cast<uint16_t>(bits16)));
+  }
+}
+// one 8-byte unit of four 16-bit values -> f32 (bf16: a shift / a mask per value)
+template <class FE>
+__device__ __forceinline__ float4 frame_f32x4(u2 q) {
+  if constexpr (std::is_same_v<FE, bf16_t>) {
+    return make_float4(__uint_as_float(q.x << 16), __uint_as_float(q.x & 0xffff0000u),
+                       __uint_as_float(q.y << 16), __uint_as_float(q.y & 0xffff0000u));
+  } else {
+    return make_float4(frame_f32<FE>(q.x & 0xffffu), frame_f32<FE>(q.x >> 16),
+                       frame_f32<FE>(q.y & 0xffffu), frame_f32<FE>(q.y >> 16));
+  }
+}
+
+// the same, non-temporal: for the read-once frame streams (a 16-bit unit of
+// 4 values is one 8-byte load, a scalar one a 2-byte load)
+template <int VEC, class FE>
+__device__ __forceinline__ void ldv_nt(const FE* p, float (&v)[VEC]) {
+  if constexpr (!std::is_same_v<FE, float>) {
+    if constexpr (VEC == 4) {
+      const float4 q = frame_f32x4<FE>(__builtin_nontemporal_load(reinterpret_cast<const u2*>(p)));
+      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+      v[0] = frame_f32<FE>(__builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p)));
+    }
+  } else if constexpr (VEC == 4) {
     using f4 = float __attribute__((ext_vector_type(4)));
     const f4 q = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
     v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
@@ -175,7 +213,8 @@ __device__ __forceinline__ void text_rows(const float* tsrc, const float* esrc, 
 // loads in flight set the time; POM's 100-row valid split spent 0.18 ms in 68
 // rounds of 4 frame loads per thread) NT = 1024 threads with 8 / 4.  NT
 // changes the f32 order of the row sums (RT = NT / CT row slots).
-template <bool MM2, int VT, int VA, int VV, int FU = 4, int TU = 4, int NT = kNT>
+// FE: the frame element type (float, f16_t or bf16_t).
+template <bool MM2, int VT, int VA, int VV, int FU = 4, int TU = 4, int NT = kNT, class FE = float>
 __global__ __launch_bounds__(NT) void utt_stream_kernel(StreamArgs a) {
   constexpr int kRF = NT * 4;  // one accumulator image: R*F <= NT*VEC
   constexpr int kSI = (kTokChunk + NT - 1) / NT;
@@ -270,7 +309,7 @@ __global__ __launch_bounds__(NT) void utt_stream_kernel(StreamArgs a) {
     for (int e = 0; e < VV; ++e) sv[e] = svv[e] = 0.f;
     if constexpr (MM2) {
       if (rA < RA) {
-        const float* base = a.audio + (i * a.L) * a.A + cA * VA;
+        const FE* base = reinterpret_cast<const FE*>(a.audio) + (i * a.L) * a.A + cA * VA;
 #pragma unroll FU
         for (int t = rA; t < a.L; t += RA) {
           float v[VA];
@@ -283,7 +322,7 @@ __global__ __launch_bounds__(NT) void utt_stream_kernel(StreamArgs a) {
         }
       }
       if (rV < RV) {
-        const float* base = a.visual + (i * a.L) * a.Vd + cV * VV;
+        const FE* base = reinterpret_cast<const FE*>(a.visual) + (i * a.L) * a.Vd + cV * VV;
 #pragma unroll FU
         for (int t = rV; t < a.L; t += RV) {
           float v[VV];
@@ -826,9 +865,36 @@ struct UttSums {
   float cnt, sw;
 };
 
-template <bool MM2, int CT, int CA, int CV, int UNR, bool NT, bool SPLIT>
+// A loaded frame column unit (4 values) as the load group holds it until its
+// frame is summed: the float4 itself, or for a 16-bit frame type the 8 bytes
+// still packed (half the registers of a group in flight), widened in accum.
+template <class FE>
+struct FrameUnit {
+  using type = u2;
+  template <bool NT>
+  static __device__ __forceinline__ u2 load(const FE* p) {
+    if constexpr (NT) {
+      return __builtin_nontemporal_load(reinterpret_cast<const u2*>(p));
+    } else {
+      return *reinterpret_cast<const u2*>(p);
+    }
+  }
+  static __device__ __forceinline__ float4 f32(u2 q) { return frame_f32x4<FE>(q); }
+};
+template <>
+struct FrameUnit<float> {
+  using type = float4;
+  template <bool NT>
+  static __device__ __forceinline__ float4 load(const float* p) { return ldnt4<NT>(p); }
+  static __device__ __forceinline__ float4 f32(float4 q) { return q; }
+};
+
+// FE: the frame element type (float, f16_t or bf16_t).
+template <bool MM2, int CT, int CA, int CV, int UNR, bool NT, bool SPLIT, class FE = float>
 __device__ __forceinline__ void utt_sums(const StreamArgs& a, int64_t i, int lane,
                                          UttSums<CT, CA, CV>& u) {
+  using FU = FrameUnit<FE>;
+  using fu_t = typename FU::type;
   const int UT = a.D >> 2, UA = a.A >> 2, UV = a.Vd >> 2;
   const float* tsrc = a.ids ? a.table : a.text_dense;
   const float* esrc = a.ids ? a.table : a.emb_dense;
@@ -862,8 +928,8 @@ __device__ __forceinline__ void utt_sums(const StreamArgs& a, int64_t i, int lan
   for (int c = 0; c < CA; ++c) sa[c] = saa[c] = z4;
 #pragma unroll
   for (int c = 0; c < CV; ++c) sv[c] = svv[c] = z4;
-  const float* abase = a.audio + i * a.L * a.A;
-  const float* vbase = a.visual + i * a.L * a.Vd;
+  const FE* abase = reinterpret_cast<const FE*>(a.audio) + i * a.L * a.A;
+  const FE* vbase = reinterpret_cast<const FE*>(a.visual) + i * a.L * a.Vd;
   const int64_t dbase = i * a.L;
   // Column offsets clamped into the row so every lane loads unconditionally:
   // lanes past a row's width read a valid duplicate and never store it.  A
@@ -878,8 +944,8 @@ __device__ __forceinline__ void utt_sums(const StreamArgs& a, int64_t i, int lan
   for (int c = 0; c < CA; ++c) ca[c] = 4 * min(lane + kWave * c, MM2 ? UA - 1 : 0);
 #pragma unroll
   for (int c = 0; c < CV; ++c) cv[c] = 4 * min(lane + kWave * c, MM2 ? UV - 1 : 0);
-  auto frame = [&](int t, float4 (&vt)[CT], float4 (&ve)[CT], float4 (&va)[CA],
-                   float4 (&vv)[CV], float& wt, bool& ok) {
+  auto frame = [&](int t, float4 (&vt)[CT], float4 (&ve)[CT], fu_t (&va)[CA],
+                   fu_t (&vv)[CV], float& wt, bool& ok) {
     const int r = __builtin_amdgcn_readlane(rid, t);
     wt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), t));
     ok = r >= 0;  // an out-of-range id (flagged) contributes a zero row
@@ -891,12 +957,12 @@ __device__ __forceinline__ void utt_sums(const StreamArgs& a, int64_t i, int lan
     }
     if constexpr (MM2) {
 #pragma unroll
-      for (int c = 0; c < CA; ++c) va[c] = ldnt4<NT>(abase + static_cast<int64_t>(t) * a.A + ca[c]);
+      for (int c = 0; c < CA; ++c) va[c] = FU::template load<NT>(abase + static_cast<int64_t>(t) * a.A + ca[c]);
 #pragma unroll
-      for (int c = 0; c < CV; ++c) vv[c] = ldnt4<NT>(vbase + static_cast<int64_t>(t) * a.Vd + cv[c]);
+      for (int c = 0; c < CV; ++c) vv[c] = FU::template load<NT>(vbase + static_cast<int64_t>(t) * a.Vd + cv[c]);
     }
   };
-  auto accum = [&](float4 (&vt)[CT], float4 (&ve)[CT], float4 (&va)[CA], float4 (&vv)[CV],
+  auto accum = [&](float4 (&vt)[CT], float4 (&ve)[CT], fu_t (&va)[CA], fu_t (&vv)[CV],
                    float wt, bool ok) {
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
@@ -910,19 +976,22 @@ __device__ __forceinline__ void utt_sums(const StreamArgs& a, int64_t i, int lan
     if constexpr (MM2) {
 #pragma unroll
       for (int c = 0; c < CA; ++c) {
-        add4(sa[c], va[c]);
-        sq4(saa[c], va[c]);
+        const float4 x = FU::f32(va[c]);
+        add4(sa[c], x);
+        sq4(saa[c], x);
       }
 #pragma unroll
       for (int c = 0; c < CV; ++c) {
-        add4(sv[c], vv[c]);
-        sq4(svv[c], vv[c]);
+        const float4 x = FU::f32(vv[c]);
+        add4(sv[c], x);
+        sq4(svv[c], x);
       }
     }
   };
   int t = 0;
   for (; t + UNR <= a.L; t += UNR) {
-    float4 vt[UNR][CT], ve[UNR][CT], va[UNR][CA], vv[UNR][CV];
+    float4 vt[UNR][CT], ve[UNR][CT];
+    fu_t va[UNR][CA], vv[UNR][CV];
     float wt[UNR];
     bool ok[UNR];
 #pragma unroll
@@ -931,7 +1000,8 @@ __device__ __forceinline__ void utt_sums(const StreamArgs& a, int64_t i, int lan
     for (int q = 0; q < UNR; ++q) accum(vt[q], ve[q], va[q], vv[q], wt[q], ok[q]);
   }
   for (; t < a.L; ++t) {
-    float4 vt[CT], ve[CT], va[CA], vv[CV];
+    float4 vt[CT], ve[CT];
+    fu_t va[CA], vv[CV];
     float wt;
     bool ok;
     frame(t, vt, ve, va, vv, wt, ok);
@@ -940,7 +1010,7 @@ __device__ __forceinline__ void utt_sums(const StreamArgs& a, int64_t i, int lan
 }
 
 template <bool MM2, int CT, int CA, int CV, int UNR = 2, bool NT = false, bool SPLIT = false,
-          bool NTS = false, int OCC = 1>
+          bool NTS = false, int OCC = 1, class FE = float>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, 8))) void utt_wave_kernel(
     StreamArgs a) {
   const int lane = threadIdx.x & (kWave - 1);
@@ -953,7 +1023,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
   for (int c = 0; c < CT; ++c) cmx[c] = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int64_t i = wid; i < a.N; i += nw) {
     UttSums<CT, CA, CV> u;
-    utt_sums<MM2, CT, CA, CV, UNR, NT, SPLIT>(a, i, lane, u);
+    utt_sums<MM2, CT, CA, CV, UNR, NT, SPLIT, FE>(a, i, lane, u);
     const float cnt = u.cnt, sw = u.sw;
     float4 (&num)[CT] = u.num;
     float4 (&sx)[CT] = u.sx;
@@ -1440,8 +1510,23 @@ static int launch_narrow(const StreamArgs& a, hipStream_t stream, int* parts) {
   return MMB_OK;
 }
 
-template <bool MM2, int CT, int CA, int CV>
+template <bool MM2, int CT, int CA, int CV, class FE = float>
 static int launch_wave(const StreamArgs& a, hipStream_t stream, int* parts = nullptr) {
+  if constexpr (!std::is_same_v<FE, float>) {
+    // 16-bit frames (mmb_mm2_stream_ft): the MMB2 policy below (4-frame
+    // groups, non-temporal frame loads), and never the narrow-frame kernel,
+    // whose packed frame loads are f32 only
+    static_assert(MM2, "16-bit frames are an MMB2 input");
+    const int grid = wave_grid(a, stream_grid_mult(), stream, parts);
+#ifndef MMB_HOOK_WAVE16_LAUNCH  // (tools/diag: the frame-group depth, MMB_FRAMES16_UNR)
+#define MMB_HOOK_WAVE16_LAUNCH false
+#endif
+    if (!(MMB_HOOK_WAVE16_LAUNCH)) {
+      utt_wave_kernel<true, CT, CA, CV, 4, true, false, false, 1, FE><<<grid, 256, 0, stream>>>(a);
+    }
+    MMB_LAUNCH_CHECK();
+    return MMB_OK;
+  }
   if (MM2 && narrow_ok(a) && narrow_variant() > 0) return launch_narrow(a, stream, parts);
   const int grid = wave_grid(a, stream_grid_mult(), stream, parts);
 #ifndef MMB_HOOK_WAVE_LAUNCH  // (tools/diag: the stream-policy sweep)
@@ -2682,7 +2767,7 @@ int stream_cu_count(hipStream_t stream) {
   return (c > 0 && c < n) ? c : n;
 }
 
-template <bool MM2, int VT, int VA, int VV>
+template <bool MM2, int VT, int VA, int VV, class FE = float>
 static int launch_stream(const StreamArgs& a, hipStream_t stream, int* parts = nullptr) {
   int grid = stream_grid(a.N, 6, stream);
   if (a.cmax_part && grid > kCmaxRows) grid = kCmaxRows;
@@ -2696,11 +2781,13 @@ static int launch_stream(const StreamArgs& a, hipStream_t stream, int* parts = n
 #ifndef MMB_HOOK_STREAM_SMALL  // (tools/diag: MMB_STREAM_SMALL)
 #define MMB_HOOK_STREAM_SMALL false
 #endif
-    if (!(MMB_HOOK_STREAM_SMALL)) {
-      utt_stream_kernel<MM2, VT, VA, VV, 16, 8><<<grid, kNT, 0, stream>>>(a);
+    bool swept = false;  // (f32 frames only)
+    if constexpr (std::is_same_v<FE, float>) swept = MMB_HOOK_STREAM_SMALL;
+    if (!swept) {
+      utt_stream_kernel<MM2, VT, VA, VV, 16, 8, kNT, FE><<<grid, kNT, 0, stream>>>(a);
     }
   } else
-    utt_stream_kernel<MM2, VT, VA, VV><<<grid, kNT, 0, stream>>>(a);
+    utt_stream_kernel<MM2, VT, VA, VV, 4, 4, kNT, FE><<<grid, kNT, 0, stream>>>(a);
   MMB_LAUNCH_CHECK();
   return MMB_OK;
 }
@@ -2911,6 +2998,59 @@ extern "C" int mmb_mm2_stream(const int32_t* ids, const float* table, int64_t v,
       s.s_out, aux_out + 2 * n, s.Kp);
   MMB_LAUNCH_CHECK();
   return MMB_OK;
+}
+
+// mmb_mm2_stream's two routes on 16-bit frames of type FE.  A frame column
+// unit is still 4 values, now 8 bytes: a modality is vector-eligible from an
+// 8-byte aligned base.
+template <class FE>
+static int stream_frames16(StreamArgs& s, int s_half, float* aux_out, uint32_t* colmax, hipStream_t stream) {
+  int parts = 0;
+  StreamVec vec = stream_vec(s);
+  vec.a = s.A % 4 == 0 && aligned8(s.audio);
+  vec.v = s.Vd % 4 == 0 && aligned8(s.visual);
+  if (vec.t && vec.a && vec.v && s.L <= kWave && s.D <= 512 && s.A <= 512 && s.Vd <= 512 &&
+      aligned16(s.num_out) && aligned16(s.s_out)) {
+    const int rc = dispatch3(s.D > 256, s.A > 256, s.Vd > 256, [&](auto ct, auto ca, auto cv) {
+      return launch_wave<true, ct.value ? 2 : 1, ca.value ? 2 : 1, cv.value ? 2 : 1, FE>(s, stream, &parts);
+    });
+    return reduce_colmax(rc, s, parts, colmax, stream);
+  }
+  MMB_REQUIRE(units_fit(s, vec));
+  s.s_half = 0;  // fp32 sums; split_rows_kernel makes them fp16 hi | lo afterwards
+  int rc = dispatch3(vec.t, vec.a, vec.v, [&](auto vt, auto va, auto vv) {
+    return launch_stream<true, vt.value ? 4 : 1, va.value ? 4 : 1, vv.value ? 4 : 1, FE>(s, stream, &parts);
+  });
+  rc = reduce_colmax(rc, s, parts, colmax, stream);
+  if (rc != MMB_OK || !s_half) return rc;
+  split_rows_kernel<<<static_cast<unsigned>(s.N), 256, s.Kp * sizeof(float), stream>>>(s.s_out, aux_out + 2 * s.N,
+                                                                                      s.Kp);
+  MMB_LAUNCH_CHECK();
+  return MMB_OK;
+}
+
+extern "C" int mmb_mm2_stream_ft(const int32_t* ids, const float* table, int64_t v, const float* wtab32,
+                                 const float* w_dense, const void* audio, const void* visual, int frame_type,
+                                 int64_t n, int t, int d, int a_, int vd, float* num_out, void* s_out,
+                                 int s_half, float* aux_out, int32_t* flag, uint32_t* colmax,
+                                 void* colmax_ws, hipStream_t stream) {
+  MMB_REQUIRE(frame_type == MMB_FRAMES_F32 || frame_type == MMB_FRAMES_F16 || frame_type == MMB_FRAMES_BF16);
+  MMB_REQUIRE(ids);  // gathered text only
+  const float* fa = static_cast<const float*>(audio);
+  const float* fv = static_cast<const float*>(visual);
+  if (frame_type == MMB_FRAMES_F32) {
+    return mmb_mm2_stream(ids, table, v, wtab32, nullptr, nullptr, w_dense, fa, fv, n, t, d, a_, vd, num_out,
+                          s_out, s_half, aux_out, flag, colmax, colmax_ws, stream);
+  }
+  StreamArgs s;
+  if (const int rc = stream_args(&s, ids, table, v, wtab32, nullptr, nullptr, w_dense, fa, fv, n, t, d, a_, vd,
+                                 num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws))
+    return rc;
+  MMB_REQUIRE(s_out && (colmax == nullptr || d <= 2 * kNT));
+  MMB_REQUIRE((reinterpret_cast<uintptr_t>(audio) & 1) == 0 && (reinterpret_cast<uintptr_t>(visual) & 1) == 0);
+  if (n == 0) return empty_call(colmax, d, stream);
+  return frame_type == MMB_FRAMES_F16 ? stream_frames16<f16_t>(s, s_half, aux_out, colmax, stream)
+                                      : stream_frames16<bf16_t>(s, s_half, aux_out, colmax, stream);
 }
 
 // Ranges per utterance of the few-long-rows path: about one workgroup per

@@ -27,6 +27,9 @@ MMB_FLAG_ID_RANGE = 1
 MMB_FLAG_ZERO_WEIGHTS = 2
 MMB_FLAG_SYNC_TIMEOUT = 4
 
+# frame element types of mmb_mm2_stream_ft
+MMB_FRAMES_F32, MMB_FRAMES_F16, MMB_FRAMES_BF16 = 0, 1, 2
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_int64
@@ -65,6 +68,8 @@ SIGNATURES = {
     "mmb_mm2_ldw": (_I, [_I]),
     "mmb_mm2_stream": (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _I,
                             _P, _P, _P, _P, _P]),
+    "mmb_mm2_stream_ft": (_I, [_P, _P, _L, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _P, _I,
+                               _P, _P, _P, _P, _P]),
     "mmb_mm2_colmax_ws_bytes": (_S, [_I]),
     "mmb_mm2_stream_split_parts": (_I, [_L, _I]),
     "mmb_mm2_stream_split_ws_bytes": (_S, [_L, _I, _I, _I, _I, _I]),

@@ -490,6 +490,32 @@ def split_ws(n: int, t: int, d: int, a: int, vd: int, device, parts: int = 0) ->
 # widest modality row of the stream kernels (mmb_mm2_stream: MMB_EINVAL past it)
 STREAM_MAX_VECTOR_WIDTH, STREAM_MAX_SCALAR_WIDTH = 1280, 320
 
+# Storage types of the audio / visual frames: the name step_plan and StepPlan
+# use -> (torch dtype, mmb_mm2_stream_ft's frame_type).  The 16-bit kinds are
+# read by the stream kernels only (mm2_stream); nothing here converts a frame.
+FRAME_KINDS = {"f32": (torch.float32, L.MMB_FRAMES_F32),
+               "f16": (torch.float16, L.MMB_FRAMES_F16),
+               "bf16": (torch.bfloat16, L.MMB_FRAMES_BF16)}
+
+
+def frame_kind(audio: torch.Tensor, visual: torch.Tensor, who: str = "mm2_stream") -> str:
+    """The FRAME_KINDS name of a pair of frame tensors; MMBError for a dtype
+    the kernels do not read or a mismatched pair (before any launch: the C
+    ABI takes bare pointers and would read the bytes as another type)."""
+    if audio.dtype != visual.dtype:
+        raise L.MMBError(f"{who}: audio is {audio.dtype} and visual {visual.dtype}; both frame "
+                         f"tensors must have one dtype")
+    for kind, (dtype, _) in FRAME_KINDS.items():
+        if audio.dtype == dtype:
+            return kind
+    raise L.MMBError(f"{who}: frames must be float32, float16 or bfloat16, not {audio.dtype}")
+
+
+def _require_f32_frames(audio, visual, who: str) -> None:
+    if frame_kind(audio, visual, who) != "f32":
+        raise L.MMBError(f"{who} reads float32 frames only, not {audio.dtype}: 16-bit frames "
+                         f"take mm2_stream (the two-kernel step)")
+
 
 def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=None,
                text_dense=None, emb_dense=None, w_dense=None, flag=None, out=None,
@@ -503,16 +529,30 @@ def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=Non
     bounds max_i |x[i, j]| (float bits) for mmb_gram_i8.  With `split` (a
     split_ws scratch) every utterance's tokens / frames are cut into `parts`
     ranges (0: split_parts) summed by their own workgroups, then added in
-    part order (mmb_mm2_stream_split: a few long rows, POM's splits)."""
+    part order (mmb_mm2_stream_split: a few long rows, POM's splits).
+
+    `audio` / `visual` may both be float16 or both bfloat16 instead of float32
+    (mmb_mm2_stream_ft; gathered text, no `split`): the outputs are bit for bit
+    those of the same frames upcast to float32."""
     kp, _ = mm2_dims(d, a, vd)
     dev = audio.device
+    kind = frame_kind(audio, visual)
+    if kind != "f32" and ids32 is None:
+        raise L.MMBError(f"mm2_stream: {kind} frames go with gathered text (ids32 + table) only")
+    if kind != "f32" and split is not None:
+        raise L.MMBError(f"mm2_stream: the split stream reads float32 frames only, not {kind}")
     text_src = table if ids32 is not None else text_dense
-    for what, w, src in (("text", d, text_src), ("audio", a, audio), ("visual", vd, visual)):
-        vec = w % 4 == 0 and src is not None and src.data_ptr() % 16 == 0
+    # a vector row: whole 4-element units from a base aligned to one unit
+    # (16 bytes of f32; 8 bytes of a 16-bit frame type)
+    unit = 16 if kind == "f32" else 8
+    for what, w, src, al in (("text", d, text_src, 16), ("audio", a, audio, unit),
+                             ("visual", vd, visual, unit)):
+        vec = w % 4 == 0 and src is not None and src.data_ptr() % al == 0
         if w > (STREAM_MAX_VECTOR_WIDTH if vec else STREAM_MAX_SCALAR_WIDTH):
             raise L.MMBError(f"mm2_stream: {what} width {w} is past the stream kernels' limit: "
                              f"{STREAM_MAX_VECTOR_WIDTH} for rows of whole float4 units (width % 4 "
-                             f"== 0, 16-byte aligned), {STREAM_MAX_SCALAR_WIDTH} otherwise")
+                             f"== 0, 16-byte aligned; 8-byte for 16-bit frames), "
+                             f"{STREAM_MAX_SCALAR_WIDTH} otherwise")
     if out is None:
         out = (torch.empty((n, d), dtype=torch.float32, device=dev),
                s_buffer(n, kp, s_half, dev),
@@ -528,6 +568,12 @@ def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=Non
                n, t, d, a, vd, L.ptr(num), L.ptr(s), int(s_half), L.ptr(aux), L.ptr(flag),
                L.ptr(colmax), L.ptr(colmax_ws), int(parts), L.ptr(split),
                split.numel() * split.element_size(), L.stream_ptr())
+        return num, s, aux
+    if kind != "f32":
+        L.call("mmb_mm2_stream_ft", L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32), L.ptr(w_dense),
+               L.ptr(audio), L.ptr(visual), FRAME_KINDS[kind][1], n, t, d, a, vd, L.ptr(num),
+               L.ptr(s), int(s_half), L.ptr(aux), L.ptr(flag), L.ptr(colmax), L.ptr(colmax_ws),
+               L.stream_ptr())
         return num, s, aux
     L.call("mmb_mm2_stream", L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32), L.ptr(text_dense),
            L.ptr(emb_dense), L.ptr(w_dense), L.ptr(audio), L.ptr(visual), n, t, d, a, vd,
@@ -569,6 +615,7 @@ def mm2_stream_project_narrow(n, t, d, a, vd, audio, visual, proj: "MMB2Projecti
                               table, wtab32, flag=None, out=None, colmax=None, colmax_ws=None):
     """a1-a8 at narrow frame widths in ONE kernel (mmb_mm2_stream_project_narrow):
     x, aux, the MMB2 rows (and the column bounds).  Returns (x, aux, mmb2)."""
+    _require_f32_frames(audio, visual, "mm2_stream_project_narrow")
     proj.enable_text_cache(table, wtab32)
     num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
     L.call("mmb_mm2_stream_project_narrow", L.ptr(ids32), L.ptr(table), table.shape[0],
@@ -584,6 +631,7 @@ def mm2_stream_project(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", id
     """a6-a8 in ONE kernel (mmb_mm2_stream_project): x, aux (and the column
     bounds) as mm2_stream, plus the MMB2 rows of mm2_project -- the sums s
     stay in LDS.  Returns (x, aux, mmb2)."""
+    _require_f32_frames(audio, visual, "mm2_stream_project")
     proj.enable_pieces()
     num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
     V = table.shape[0] if table is not None else 0
@@ -744,6 +792,7 @@ class StepPlan(NamedTuple):
     bounds: tuple     # row chunks ((r0, r1), ...)
     step_rows: int    # rows of a full chunk
     s_half: bool      # s as fp16 hi | lo planes (the x3 projection)
+    frames: str = "f32"  # storage type of the audio / visual frames (FRAME_KINDS)
 
     @property
     def remove_launch(self) -> bool:
@@ -755,15 +804,21 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
               chunks: int | None = None, fuse_remove: bool = True, gram_kind: str | None = None,
               stream_project: bool | None = None, narrow_fused: bool | None = None,
               fork_projection: bool | None = None, split_stream: bool | None = None,
-              split_projection: bool = True) -> StepPlan:
+              split_projection: bool = True, frames: str = "f32") -> StepPlan:
     """The plan of a step over `n` of a split's `n_total` utterances on a chip
     of `cus` CUs; the remaining arguments are FusedStep's overrides (None: by
     shape).  Precedence: the fused front kernels need one chunk ASKED for and
     the fp16 split, the wide-frame one first; fewer utterances than features
     force one chunk (the transposed branch needs X^T Omega of all rows); the
     projection forks or takes the removal only behind the plain stream kernel,
-    in one chunk, at npc = 1."""
+    in one chunk, at npc = 1.  16-bit `frames` ("f16" / "bf16") are read by
+    the plain stream kernel only: the front is "stream" and never split,
+    whatever the three overrides that allow the other fronts say."""
     check_npc(npc)
+    if frames not in FRAME_KINDS:
+        raise ValueError(f"frames must be one of {', '.join(FRAME_KINDS)}, not {frames!r}")
+    if frames != "f32":
+        stream_project = narrow_fused = split_stream = False
     s_half = L.query("mmb_mm2_ldw", d) <= 320
     one_asked = (chunks or 1) == 1
     if stream_project is None:
@@ -812,7 +867,7 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
     split = bool((split_stream is None or split_stream) and front == "stream" and one
                  and t > 64 and 0 < n <= cus)
     proj_split = bool(split_projection and front == "stream" and s_half and one)
-    return StepPlan(front, split, gram, project, proj_split, bounds, step, s_half)
+    return StepPlan(front, split, gram, project, proj_split, bounds, step, s_half, frames)
 
 
 # the fused front kernels: trace phase and mirror
@@ -889,11 +944,15 @@ class FusedStep:
         self.allreduce = allreduce
         self.n_total = self.n if n_total is None else n_total
         self.row0 = row0
+        # the frames' storage type, checked here: a step never launches on a
+        # dtype its kernels would read as another
+        self.frames = frame_kind(inputs["audio"], inputs["visual"], "FusedStep")
         self.plan = p = step_plan(self.n, self.n_total, self.t, self.d, self.a, self.vd, self.V, npc,
                                   L.cu_count(dev), chunks=chunks, fuse_remove=fuse_remove,
                                   gram_kind=gram_kind, stream_project=stream_project,
                                   narrow_fused=narrow_fused, fork_projection=fork_projection,
-                                  split_stream=split_stream, split_projection=split_projection)
+                                  split_stream=split_stream, split_projection=split_projection,
+                                  frames=self.frames)
         self.proj = MMB2Projection(networks, self.d, self.a, self.vd, self.t, dev)
         kp = self.proj.kp
         self.x = torch.empty((self.n, self.d), dtype=torch.float32, device=dev)

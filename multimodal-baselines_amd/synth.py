@@ -79,7 +79,8 @@ def frames(N: int, T: int, F: int, seed: int = 0, pad_frac: float = 0.0) -> np.n
 # ---------------------------------------------------------------- device side
 def device_workload(N: int, T: int, V: int, D: int = 300, A: int = 300, Vd: int = 300,
                     seed: int = 0, device="cuda", s: float = 1.1, w0: float = 1.0,
-                    mean_len: float | None = None, poisson_len: float | None = None):
+                    mean_len: float | None = None, poisson_len: float | None = None,
+                    frame_dtype=None):
     """Config-3 workload generated directly in device memory (torch RNG).
 
     Returns dict of device tensors: table [V,D] f32, wtab [V] f32 (the f32
@@ -90,6 +91,9 @@ def device_workload(N: int, T: int, V: int, D: int = 300, A: int = 300, Vd: int 
     `mean_len` -- POM-like lengths ~ N(mean, mean/1.5) clipped to [1, T];
     `poisson_len` -- SURVEY §8d's second configs[3] run, Poisson(mean) lengths
     clipped to [1, T] (T = 64 there).  The result then also holds `lengths` [N].
+
+    `frame_dtype` (torch.float16 / torch.bfloat16): the same frames rounded to
+    16-bit storage (round to nearest even; the -10 pads are exact in both).
     """
     import torch
 
@@ -114,6 +118,9 @@ def device_workload(N: int, T: int, V: int, D: int = 300, A: int = 300, Vd: int 
     visual = torch.empty(N, T, Vd, device=device, dtype=torch.float32)
     audio.uniform_(-1.0, 1.0, generator=gen)
     visual.uniform_(-1.0, 1.0, generator=gen)
+    if frame_dtype is not None and frame_dtype != torch.float32:
+        audio = audio.to(frame_dtype)
+        visual = visual.to(frame_dtype)
     out = {"table": table, "wtab": wtab, "ids": ids, "audio": audio, "visual": visual}
     lens = None
     if mean_len is not None:

@@ -31,6 +31,8 @@ template <class A>
 bool diag_narrow_launch(int var, const A& a, int grid, hipStream_t stream);
 template <bool MM2, int CT, int CA, int CV, class A>
 bool diag_wave_launch(const A& a, int grid, hipStream_t stream);
+template <int CT, int CA, int CV, class FE, class A>
+bool diag_wave16_launch(const A& a, int grid, hipStream_t stream);
 template <class F>
 bool diag_fused_launch(const F& f, int grid, hipStream_t stream);
 template <bool MM2, int VT, int VA, int VV, class A>
@@ -55,6 +57,7 @@ static __device__ unsigned long long g_fused_probe[1024 * kFProbe];
 #define MMB_HOOK_NARROW_VARIANT diag_knob("MMB_STREAM_NARROW", 10)
 #define MMB_HOOK_NARROW_LAUNCH diag_narrow_launch(var, a, grid, stream)
 #define MMB_HOOK_WAVE_LAUNCH diag_wave_launch<MM2, CT, CA, CV>(a, grid, stream)
+#define MMB_HOOK_WAVE16_LAUNCH diag_wave16_launch<CT, CA, CV, FE>(a, grid, stream)
 #define MMB_HOOK_FUSED_WAIT_ITERS g_fused_wait_iters
 #define FUSED_PROBE(slot)                                                              \
   do {                                                                                 \

@@ -43,6 +43,18 @@ bool diag_wave_launch(const A& a, int grid, hipStream_t stream) {
   return true;
 }
 
+// launch_wave on 16-bit frames with MMB_FRAMES16_UNR: frames per load group
+// (the product runs 4; the sums do not depend on it)
+template <int CT, int CA, int CV, class FE, class A>
+bool diag_wave16_launch(const A& a, int grid, hipStream_t stream) {
+  switch (diag_knob("MMB_FRAMES16_UNR", 4)) {
+    case 6: utt_wave_kernel<true, CT, CA, CV, 6, true, false, false, 1, FE><<<grid, 256, 0, stream>>>(a); break;
+    case 8: utt_wave_kernel<true, CT, CA, CV, 8, true, false, false, 1, FE><<<grid, 256, 0, stream>>>(a); break;
+    default: return false;
+  }
+  return true;
+}
+
 // launch_fused with the MMB_FUSED_* knobs (read per launch: in-process sweeps):
 // MMB_FUSED_UNR streamer frames per load group, MMB_FUSED_DIAG timing-only
 // ablations, MMB_FUSED_PIPE streamer pipelining, MMB_FUSED_SLOTS ring slots

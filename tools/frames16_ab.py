@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""Same-process A/B of whole steps on f32 and on 16-bit audio / visual frames.
+
+Variants, interleaved round by round on one workload (the 16-bit frames are
+the f32 ones rounded; they live beside them in HBM):
+
+    f32_default     the product's step on f32 frames (the fused stream +
+                    projection kernel at wide frames, the narrow fused kernel
+                    at MOSI widths)
+    f32_two_kernel  stream kernel -> s in HBM -> projection, f32 frames
+    bf16, f16       the step on 16-bit frames (always the two-kernel step:
+                    mmb_mm2_stream_ft)
+
+Per-phase HIP event times, median per variant; for the front kernel of every
+variant its algorithmic HBM bytes per utterance (rows read once,
+outputs written once) and the fraction of the 8 TB/s peak they make.
+
+    python tools/frames16_ab.py                      # configs[3]: 1M x 40 x 300 / 300 / 300, V = 400k
+    python tools/frames16_ab.py --T 20 --A 76 --Vd 48 --V 3016     # the MOSI shape
+    python tools/frames16_ab.py --unr 6 8    # the tools build (make diag): also the 16-bit wave kernel
+                                             # at 6 / 8 frames per load group (the product runs 4)
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multimodal-baselines_amd"))
+
+import torch  # noqa: E402
+
+import mmb_lib  # noqa: E402
+import models  # noqa: E402
+import pipeline as P  # noqa: E402
+import synth  # noqa: E402
+
+PEAK = 8.0e12  # HBM bytes / s
+D = 300
+DIAG_LIB = os.path.join(ROOT, "tools", "diag", "libmmb_diag.so")
+UNR_KNOB = "MMB_FRAMES16_UNR"  # read per launch by the tools build
+
+
+def front_bytes(step) -> int:
+    """Algorithmic HBM bytes per utterance of the step's front kernel: T rows
+    of every modality and T ids read; x, aux and s (two-kernel) or the MMB2
+    row (fused fronts) written."""
+    esize = P.FRAME_KINDS[step.frames][0].itemsize
+    read = step.t * (4 * step.d + esize * (step.a + step.vd) + 4)
+    out = 4 * step.d + 12
+    out += 4 * step.proj.kp if step.plan.front == "stream" else 4 * step.d
+    return read + out
+
+
+def to_kind(inp: dict, dtype, rows: int = 1 << 16) -> dict:
+    """`inp` with its frames rounded to `dtype`, converted in row chunks."""
+    out = dict(inp)
+    for key in ("audio", "visual"):
+        src = inp[key]
+        dst = torch.empty(src.shape, dtype=dtype, device=src.device)
+        for r in range(0, src.shape[0], rows):
+            dst[r:r + rows] = src[r:r + rows]
+        out[key] = dst
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--T", type=int, default=40)
+    ap.add_argument("--A", type=int, default=300)
+    ap.add_argument("--Vd", type=int, default=300)
+    ap.add_argument("--V", type=int, default=400_000)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--unr", type=int, nargs="*", default=[],
+                    help="tools build: also time the bf16 / f16 steps at these frame-group depths")
+    args = ap.parse_args()
+    if args.unr:
+        mmb_lib.load(DIAG_LIB)  # the tools build: explicit, never through the product loader
+    dev = torch.device("cuda", 0)
+    inp = synth.device_workload(args.n, args.T, args.V, A=args.A, Vd=args.Vd, seed=4000, device=dev)
+    torch.manual_seed(0)
+    gen = models.AudioVisualGeneratorMultimodal(D, args.A, args.Vd, norm=None).to(dev)
+    nets = gen.networks()
+    steps = {"f32_default": P.FusedStep(inp, nets),
+             "f32_two_kernel": P.FusedStep(inp, nets, stream_project=False, narrow_fused=False),
+             "bf16": P.FusedStep(to_kind(inp, torch.bfloat16), nets),
+             "f16": P.FusedStep(to_kind(inp, torch.float16), nets)}
+    knob = {k: None for k in steps}
+    for u in args.unr:  # the same steps (and buffers), launched at another depth
+        for k in ("bf16", "f16"):
+            steps[f"{k}_unr{u}"], knob[f"{k}_unr{u}"] = steps[k], str(u)
+
+    def run(k, **kw):
+        if knob[k] is None:
+            os.environ.pop(UNR_KNOB, None)
+        else:
+            os.environ[UNR_KNOB] = knob[k]
+        return steps[k].run(**kw)
+
+    print(f"shape: n {args.n} T {args.T} D {D} A {args.A} Vd {args.Vd} V {args.V}; "
+          f"HBM in use {torch.cuda.memory_allocated(dev) / 2 ** 30:.1f} GiB", flush=True)
+    rows = {}
+    for k, st in steps.items():
+        run(k)
+        torch.cuda.synchronize()
+        st.check()
+        if knob[k] is None:
+            rows[k] = st.mmb2.clone() if args.unr and st.frames != "f32" else None
+        else:  # the depth changes no sum
+            assert torch.equal(st.mmb2, rows[k.split("_")[0]]), k
+        print(f"{k}: front {st.plan.front}, projection {st.plan.project}, gram {st.plan.gram}, "
+              f"frames {st.plan.frames}", flush=True)
+    # what the rounding costs here: the 16-bit steps' rows against the f32 two-kernel step's
+    ref = steps["f32_two_kernel"]
+    for k in ("bf16", "f16"):
+        st = steps[k]
+        run(k)
+        rel =((st.mmb2 - ref.mmb2).abs().amax(1) / ref.mmb2.abs().amax(1)).max().item()
+        print(f"{k}: x equal to f32 {torch.equal(st.x, ref.x)}; MMB2 rows move by {rel:.2e} row-relative "
+              f"(the frames' rounding)", flush=True)
+    res = {k: {} for k in steps}
+    for r in range(args.rounds):
+        for k, st in steps.items():
+            tr = {}
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.steps):
+                run(k, trace=tr)
+            e1.record()
+            torch.cuda.synchronize()
+            res[k].setdefault("step", []).append(e0.elapsed_time(e1) / args.steps)
+            for ph, evs in tr.items():
+                res[k].setdefault(ph, []).append(sum(x.elapsed_time(y) for x, y in evs) / args.steps)
+        print(f"round {r}: " + "  ".join(f"{k} {res[k]['step'][-1]:.3f} ms" for k in steps), flush=True)
+    for k in steps:
+        print(k + ": " + ", ".join(f"{ph} {statistics.median(v):.3f}" for ph, v in res[k].items()))
+    print("\n| variant | front kernel | step ms (min .. max) | front ms | KB / utterance | of 8 TB/s |")
+    print("|---|---|---|---|---|---|")
+    for k, st in steps.items():
+        phase = "mm2_stream" if st.plan.front == "stream" else P._FRONTS[st.plan.front][0]
+        ms = statistics.median(res[k][phase])
+        b = front_bytes(st)
+        frac = b * args.n / (ms * 1e-3) / PEAK
+        sp = res[k]["step"]
+        print(f"| {k} | {phase} | {statistics.median(sp):.2f} ({min(sp):.2f} .. {max(sp):.2f}) | {ms:.2f} | "
+              f"{b / 1e3:.1f} | {frac:.3f} |")
+
+
+if __name__ == "__main__":
+    main()
