@@ -1288,9 +1288,7 @@ namespace mmb {
 //   contiguous 2d + 4 floats) | hot_slot1 [v] int32 (slot + 1, 0 = not hot) |
 //   hot_ids [kTextHot] int32 | w [v] f32 (a copy of the weights: the fused
 //   kernel reads all of it through one buffer descriptor)
-constexpr int kTextLdp = 304;   // P columns kept (d + 1 <= 304)
-constexpr int kTextLdq = 608;   // cache row stride (floats): 2 d + 4 <= 608, 16-byte rows
-constexpr int kTextHot = 32;    // words whose rows live in LDS
+// (kTextLdp, kTextLdq, kTextHot: mmb_common.h, shared with that kernel)
 constexpr int64_t kTextMaxV = 16384;
 
 __global__ __launch_bounds__(320) void mm2_text_table_kernel(const float* __restrict__ E, int D,

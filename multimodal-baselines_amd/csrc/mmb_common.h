@@ -145,6 +145,13 @@ inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7
 // points) must agree on it; mmb_mm2_k rounds the SUM of the widths instead.
 __host__ __device__ constexpr int piece_k(int w) { return (2 * w + 31) / 32 * 32; }
 
+// The text cache's layout, on which its writer (mmb_mm2_text_cache,
+// mm2_kernels.hip) and its reader (utt_narrow_fused_kernel,
+// narrow_fused_kernels.hip) must agree in the same way.
+constexpr int kTextLdp = 304;   // P columns kept (d + 1 <= 304)
+constexpr int kTextLdq = 608;   // cache row stride (floats): 2 d + 4 <= 608, 16-byte rows
+constexpr int kTextHot = 32;    // words whose rows live in LDS
+
 // Allows Kernel `bytes` of dynamic LDS (more than the default 64 KB), once per
 // process, before its first launch.  One flag per kernel: every kernel
 // (instantiation) is its own instantiation of this function.  A failure shows

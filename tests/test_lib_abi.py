@@ -69,6 +69,7 @@ def test_product_sources_carry_no_tools_code():
     csrc = os.path.join(ROOT, "multimodal-baselines_amd", "csrc")
     srcs = [f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".cpp"))]
     assert "sif_kernels.hip" in srcs and "pc_kernels.hip" in srcs
+    assert "fused_kernels.hip" in srcs and "narrow_fused_kernels.hip" in srcs
     for f in srcs:
         text = open(os.path.join(csrc, f)).read()
         assert "getenv" not in text, f
@@ -76,7 +77,8 @@ def test_product_sources_carry_no_tools_code():
         for m in macros:
             assert m not in text, (f, m)
     # the tails the tools build includes exist; the product's target is empty
-    for tail in ("sif_tail.inc", "pc_tail.inc", "mm2_tail.inc", "diag_hooks.h"):
+    for tail in ("sif_tail.inc", "fused_tail.inc", "narrow_fused_tail.inc", "pc_tail.inc", "mm2_tail.inc",
+                 "diag_hooks.h"):
         assert os.path.exists(os.path.join(ROOT, "tools", "diag", tail)), tail
     code = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "mmb_no_tools.h")).read())
     assert code.strip() == ""

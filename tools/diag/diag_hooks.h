@@ -3,7 +3,7 @@
 // MMB_HOOK_* point in multimodal-baselines_amd/csrc/ compiles its product
 // default unless defined here; the definitions behind the hooks (variant
 // kernels, sweep launches, knobs, mmb_diag_* entry points) are in
-// tools/diag/{sif,pc,mm2}_tail.inc, included at the end of the product
+// tools/diag/{sif,fused,narrow_fused,pc,mm2}_tail.inc, included at the end of the product
 // sources through MMB_TOOLS_TAIL_*.  The product library (`make`) sees none
 // of this and reads no environment variable.  Test and timing
 // infrastructure, not product code.
@@ -33,31 +33,34 @@ template <bool MM2, int CT, int CA, int CV, class A>
 bool diag_wave_launch(const A& a, int grid, hipStream_t stream);
 template <int CT, int CA, int CV, class FE, class A>
 bool diag_wave16_launch(const A& a, int grid, hipStream_t stream);
-template <class F>
-bool diag_fused_launch(const F& f, int grid, hipStream_t stream);
 template <bool MM2, int VT, int VA, int VV, class A>
 bool diag_stream_small(const A& a, int grid, hipStream_t stream);
-template <class F>
-void diag_fused_args(F& f) {
-  f.balanced = diag_knob("MMB_FUSED_BALANCED", 1);
-  if (diag_knob("MMB_FUSED_DYN", 1) == 0) f.sched = nullptr;
-}
-template <int I = 0>
-void diag_nf_teams_attr();
-template <class F>
-bool diag_nf_teams_launch(int teams, const F& f, int64_t grid, hipStream_t stream);
-// a test shortens the fused kernel's bounded waits (mmb_diag_fused_wait_iters)
-static __device__ int g_fused_wait_iters = 1 << 23;
-// per-workgroup wall-clock marks of the fused kernel (start; each streamer
-// wave's and each projector wave's end), read back with mmb_diag_fused_probe
-constexpr int kFProbe = 9;
-static __device__ unsigned long long g_fused_probe[1024 * kFProbe];
 
 #define MMB_HOOK_STREAM_GRID_MULT diag_stream_grid_mult()
 #define MMB_HOOK_NARROW_VARIANT diag_knob("MMB_STREAM_NARROW", 10)
 #define MMB_HOOK_NARROW_LAUNCH diag_narrow_launch(var, a, grid, stream)
 #define MMB_HOOK_WAVE_LAUNCH diag_wave_launch<MM2, CT, CA, CV>(a, grid, stream)
 #define MMB_HOOK_WAVE16_LAUNCH diag_wave16_launch<CT, CA, CV, FE>(a, grid, stream)
+#define MMB_HOOK_STREAM_SMALL diag_stream_small<MM2, VT, VA, VV>(a, grid, stream)
+#define MMB_TOOLS_TAIL_SIF "../../tools/diag/sif_tail.inc"
+
+// ---- fused_kernels.hip -------------------------------------------------------
+template <class F>
+bool diag_fused_launch(const F& f, int grid, hipStream_t stream);
+template <class F>
+void diag_fused_args(F& f) {
+  f.balanced = diag_knob("MMB_FUSED_BALANCED", 1);
+  if (diag_knob("MMB_FUSED_DYN", 1) == 0) f.sched = nullptr;
+}
+// a test shortens the fused kernel's bounded waits (mmb_diag_fused_wait_iters)
+// (static: a copy per translation unit -- the kernel reads its own unit's, so
+// the entry points that set and read them are in fused_tail.inc)
+static __device__ int g_fused_wait_iters = 1 << 23;
+// per-workgroup wall-clock marks of the fused kernel (start; each streamer
+// wave's and each projector wave's end), read back with mmb_diag_fused_probe
+constexpr int kFProbe = 9;
+static __device__ unsigned long long g_fused_probe[1024 * kFProbe];
+
 #define MMB_HOOK_FUSED_WAIT_ITERS g_fused_wait_iters
 #define FUSED_PROBE(slot)                                                              \
   do {                                                                                 \
@@ -65,12 +68,19 @@ static __device__ unsigned long long g_fused_probe[1024 * kFProbe];
       g_fused_probe[blockIdx.x * kFProbe + (slot)] = wall_clock64();                   \
   } while (0)
 #define MMB_HOOK_FUSED_LAUNCH diag_fused_launch(f, grid, stream)
-#define MMB_HOOK_STREAM_SMALL diag_stream_small<MM2, VT, VA, VV>(a, grid, stream)
 #define MMB_HOOK_FUSED_ARGS(f) diag_fused_args(f)
+#define MMB_TOOLS_TAIL_FUSED "../../tools/diag/fused_tail.inc"
+
+// ---- narrow_fused_kernels.hip ------------------------------------------------
+template <int I = 0>
+void diag_nf_teams_attr();
+template <class F>
+bool diag_nf_teams_launch(int teams, const F& f, int64_t grid, hipStream_t stream);
+
 #define MMB_HOOK_NF_TEAMS diag_knob("MMB_NF_TEAMS", 0)
 #define MMB_HOOK_NF_TEAMS_ATTR diag_nf_teams_attr()
 #define MMB_HOOK_NF_TEAMS_LAUNCH diag_nf_teams_launch(teams, f, grid, stream)
-#define MMB_TOOLS_TAIL_SIF "../../tools/diag/sif_tail.inc"
+#define MMB_TOOLS_TAIL_NARROW_FUSED "../../tools/diag/narrow_fused_tail.inc"
 
 // ---- pc_kernels.hip ----------------------------------------------------------
 // a test shortens the solve's bounded waits (mmb_diag_pc_wait_iters) and names
