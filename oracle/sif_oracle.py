@@ -160,7 +160,7 @@ def pc_from_gram(G, z0, npc=1, transposed=False, n_iter=7):
 
 
 def sliced_gram(X, colmax=None):
-    """CPU restatement of the int8 Gram (csrc/pc_kernels.hip gram_i8l_kernel;
+    """CPU restatement of the int8 Gram (csrc/gram_kernels.hip gram_i8l_kernel;
     r04's gram_i8_kernel had the same digits and pairs): each value a 30-bit
     fixed-point integer of its column's power-of-two bound 2^e (|x| <= colmax
     < 2^e), v = rint(x 2^(30-e)), cut into four balanced base-256 digits (top

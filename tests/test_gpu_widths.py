@@ -3,9 +3,10 @@
 The drop-ins (sif_functions.compute_pc / remove_pc / get_weighted_average,
 sif.get_sentence_embeddings) take an X or a word table of any width; under
 them libmmb dispatches on the width d, the row count n, npc and pointer
-alignment (csrc/pc_kernels.hip: mmb_gram's three routes, the X^T Omega wave /
-generic kernels, the multi- and single-workgroup solvers, the vector / scalar
-removal; csrc/sif_kernels.hip: the wave / workgroup weighted average).  The
+alignment (csrc/gram_kernels.hip: mmb_gram's three routes; csrc/pc_kernels.hip:
+the X^T Omega wave / generic kernels, the multi- and single-workgroup solvers;
+csrc/pc_remove_kernels.hip: the vector / scalar removal; csrc/sif_kernels.hip:
+the wave / workgroup weighted average).  The
 shape table of tests/width_cases.py holds the smallest shapes at which each
 route, partial tile and threshold is reached; every comparison is against
 plain f64 numpy or the CPU oracle of the same operation, at the bar the

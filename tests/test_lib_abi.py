@@ -70,6 +70,7 @@ def test_product_sources_carry_no_tools_code():
     srcs = [f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".cpp"))]
     assert "sif_kernels.hip" in srcs and "pc_kernels.hip" in srcs
     assert "fused_kernels.hip" in srcs and "narrow_fused_kernels.hip" in srcs
+    assert "gram_kernels.hip" in srcs and "pc_remove_kernels.hip" in srcs and "mmb_pc.h" in srcs
     for f in srcs:
         text = open(os.path.join(csrc, f)).read()
         assert "getenv" not in text, f
@@ -78,10 +79,34 @@ def test_product_sources_carry_no_tools_code():
             assert m not in text, (f, m)
     # the tails the tools build includes exist; the product's target is empty
     for tail in ("sif_tail.inc", "fused_tail.inc", "narrow_fused_tail.inc", "pc_tail.inc", "mm2_tail.inc",
-                 "diag_hooks.h"):
+                 "gram_tail.inc", "pc_remove_tail.inc", "diag_hooks.h"):
         assert os.path.exists(os.path.join(ROOT, "tools", "diag", tail)), tail
     code = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "mmb_no_tools.h")).read())
     assert code.strip() == ""
+
+
+def test_pc_solve_workspace_layout():
+    """control words | tiles | G2 | z0, laid out once (SolveWs, csrc/pc_kernels.hip):
+    16 + 2 (d / 16 + 1) 4096 + 8 d^2 + 128 d bytes; a negative d sizes as d = 0."""
+    for d in (0, 1, 15, 16, 17, 300, 320):
+        assert mmb_lib.query("mmb_pc_solve_mc_ws_bytes", d) == \
+            16 + 2 * (d // 16 + 1) * 4096 + 8 * d * d + 128 * d, d
+    assert mmb_lib.query("mmb_pc_solve_mc_ws_bytes", 0) == 8_208
+    assert mmb_lib.query("mmb_pc_solve_mc_ws_bytes", 16) == 20_496
+    assert mmb_lib.query("mmb_pc_solve_mc_ws_bytes", 300) == 914_064
+    assert mmb_lib.query("mmb_pc_solve_mc_ws_bytes", 320) == 1_032_208
+    for d in (-1, -300):
+        assert mmb_lib.query("mmb_pc_solve_mc_ws_bytes", d) == 8_208, d
+
+
+def test_gram_workspace_sizes_are_pinned():
+    """mmb_gram_workspace_bytes (csrc/gram_kernels.hip: the largest of its four
+    planners' partials) as the library returned it before the Gram sources
+    were split out of pc_kernels.hip."""
+    pinned = {(1, 4): 32_768, (1284, 300): 9_338_880, (4097, 300): 24_903_680,
+              (1_000_000, 300): 62_914_560, (1000, 301): 6_225_920, (1000, 512): 17_301_504}
+    for (n, d), want in pinned.items():
+        assert mmb_lib.query("mmb_gram_workspace_bytes", n, d) == want, (n, d)
 
 
 def test_library_carries_gfx950_code_objects():

@@ -18,7 +18,8 @@ from oracle import sif_oracle as O
 N_OVERSAMPLES = 10
 NPCS = (1, 2, 6)
 
-# (n, d): what each shape reaches in the dispatch of csrc/pc_kernels.hip
+# (n, d): what each shape reaches in the dispatch of csrc/gram_kernels.hip,
+# csrc/pc_kernels.hip (X^T Omega, the solvers) and csrc/pc_remove_kernels.hip
 SHAPES = [
     (2, 2), (40, 2),                        # smallest d; one solver workgroup; block wider than the space
     (3, 5), (600, 5),                       # d < k, transposed and direct

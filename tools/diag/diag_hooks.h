@@ -3,7 +3,7 @@
 // MMB_HOOK_* point in multimodal-baselines_amd/csrc/ compiles its product
 // default unless defined here; the definitions behind the hooks (variant
 // kernels, sweep launches, knobs, mmb_diag_* entry points) are in
-// tools/diag/{sif,fused,narrow_fused,pc,mm2}_tail.inc, included at the end of the product
+// tools/diag/{sif,fused,narrow_fused,gram,pc,pc_remove,mm2}_tail.inc, included at the end of the product
 // sources through MMB_TOOLS_TAIL_*.  The product library (`make`) sees none
 // of this and reads no environment variable.  Test and timing
 // infrastructure, not product code.
@@ -82,11 +82,7 @@ bool diag_nf_teams_launch(int teams, const F& f, int64_t grid, hipStream_t strea
 #define MMB_HOOK_NF_TEAMS_LAUNCH diag_nf_teams_launch(teams, f, grid, stream)
 #define MMB_TOOLS_TAIL_NARROW_FUSED "../../tools/diag/narrow_fused_tail.inc"
 
-// ---- pc_kernels.hip ----------------------------------------------------------
-// a test shortens the solve's bounded waits (mmb_diag_pc_wait_iters) and names
-// one workgroup that never arrives (mmb_diag_pc_skip_arrival)
-static __device__ int g_pm_wait_iters = 1 << 20;
-static __device__ int g_pm_skip_wg = -1;
+// ---- gram_kernels.hip --------------------------------------------------------
 inline void diag_gram_ranges(int& r) {
   const int v = diag_knob("MMB_GRAM_RANGES", 0);  // A/B: ranges (<= 128)
   if (v > 0) r = std::max(r, std::min(v, 128));
@@ -95,22 +91,36 @@ bool diag_gram_i8_v1(int& rc, const float* x, const uint32_t* colmax, int64_t n,
                      int accumulate, double* part, hipStream_t stream);
 int diag_gram_i8_block(const float* xb, const uint32_t* colmax, int64_t nb, int d, double* g, int acc,
                        double* part, hipStream_t stream);
-bool diag_solve_launch(int& rc, const double* g, double* g2, int nsq_wg, int d, const double* z0, int k,
-                       int npc, int n_iter, int transposed, double* pc_out, double* xbuf, unsigned* ctl,
-                       int32_t* flag, int T, hipStream_t stream);
-bool diag_pc_remove_launch(int rr, int grid, hipStream_t stream, const float* num, const float* cnt,
-                           int64_t n, int d, const double* pc, float* out32);
 
-#define MMB_HOOK_PM_WAIT_ITERS g_pm_wait_iters
-#define MMB_HOOK_PM_SKIP_ARRIVAL (static_cast<int>(blockIdx.x) == g_pm_skip_wg)
-#define MMB_HOOK_PC_REMOVE_R diag_knob("MMB_PC_REMOVE_R", 4)
 #define MMB_HOOK_GRAM_RANGES(r) diag_gram_ranges(r)
 #define MMB_HOOK_GRAM_I8(rc) diag_gram_i8_v1(rc, x, colmax, n, d, g, accumulate, part, stream)
 #define MMB_HOOK_GRAM_I8_BLOCK diag_gram_i8_block
+#define MMB_TOOLS_TAIL_GRAM "../../tools/diag/gram_tail.inc"
+
+// ---- pc_kernels.hip ----------------------------------------------------------
+// a test shortens the solve's bounded waits (mmb_diag_pc_wait_iters) and names
+// one workgroup that never arrives (mmb_diag_pc_skip_arrival)
+// (static: a copy per translation unit -- pc_solve_mc_kernel reads its own
+// unit's, so the entry points that set them are in pc_tail.inc)
+static __device__ int g_pm_wait_iters = 1 << 20;
+static __device__ int g_pm_skip_wg = -1;
+bool diag_solve_launch(int& rc, const double* g, double* g2, int nsq_wg, int d, const double* z0, int k,
+                       int npc, int n_iter, int transposed, double* pc_out, double* xbuf, unsigned* ctl,
+                       int32_t* flag, int T, hipStream_t stream);
+
+#define MMB_HOOK_PM_WAIT_ITERS g_pm_wait_iters
+#define MMB_HOOK_PM_SKIP_ARRIVAL (static_cast<int>(blockIdx.x) == g_pm_skip_wg)
 #define MMB_HOOK_SOLVE_LAUNCH(rc) \
   diag_solve_launch(rc, g, g2, nsq_wg, d, z0, k, npc, n_iter, transposed, pc_out, xbuf, ctl, flag, T, stream)
-#define MMB_HOOK_PC_REMOVE_LAUNCH diag_pc_remove_launch(rr, grid, stream, num, cnt, n, d, pc, out32)
 #define MMB_TOOLS_TAIL_PC "../../tools/diag/pc_tail.inc"
+
+// ---- pc_remove_kernels.hip ---------------------------------------------------
+bool diag_pc_remove_launch(int rr, int grid, hipStream_t stream, const float* num, const float* cnt,
+                           int64_t n, int d, const double* pc, float* out32);
+
+#define MMB_HOOK_PC_REMOVE_R diag_knob("MMB_PC_REMOVE_R", 4)
+#define MMB_HOOK_PC_REMOVE_LAUNCH diag_pc_remove_launch(rr, grid, stream, num, cnt, n, d, pc, out32)
+#define MMB_TOOLS_TAIL_PC_REMOVE "../../tools/diag/pc_remove_tail.inc"
 
 // ---- mm2_kernels.hip ---------------------------------------------------------
 template <int CT>
