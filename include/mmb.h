@@ -549,13 +549,19 @@ int mmb_word_logprob_backward(const float* latents, int64_t b, int d, int64_t v,
                               const float* dlp, float* dlat, hipStream_t stream);
 
 /* stats [n][3][f] f64 = per-utterance masked frame sums (sum_t m, sum_t m x,
- * sum_t m x^2) of x [n,t,f] (mask nullable = ones); streamed once per split. */
+ * sum_t m x^2) of x [n,t,f] (mask nullable = ones); streamed once per split.
+ * n = 0 writes nothing (x and stats may be null); t = 0 writes zeros (x may be
+ * null). */
 int mmb_gauss_stats(const float* x, const float* mask, int64_t n, int t, int f, double* stats,
                     hipStream_t stream);
 /* lp[k][b] = get_normal_log_prob(mu_k[b], sigma_k[b], x, mask) for combination
  * k of modalities mods[k] (bit 0 text, 1 audio, 2 visual; features in that
  * torch.cat order), from the stats of rows idx[b] (idx nullable = b).
  * stats[3] / fm[3] / mods / mu / sigma are HOST arrays (of device pointers).
+ * Only sigma^2 and |sigma| enter (the reference's log(1 / sqrt(2 pi sigma^2))):
+ * sigma's sign does not matter to lp, and the gradients below are those of
+ * that lp for either sign (sigma != 0).  b = 0 returns MMB_OK with nothing
+ * launched (the device pointers may then be null).
  * replaces: losses.get_normal_log_prob /root/reference/losses.py:13-33 and the
  *           per-modality loop of get_log_prob_matrix :249-256               */
 int mmb_gauss_loglik(const double* const* stats, const int* fm, const int64_t* idx, int64_t b,

@@ -20,7 +20,7 @@
 //     (Wn = W / max(|W|, 1e-8), torch's cosine_similarity).
 //   * the Gaussian term is a function of the per-utterance masked frame sums
 //     M0 = sum_t m, M1 = sum_t m x, M2 = sum_t m x^2 only:
-//       lp = sum_f M0 (-log s - log(2 pi)/2) - (M2 - 2 mu M1 + mu^2 M0) / (2 s^2),
+//       lp = sum_f M0 (-log |s| - log(2 pi)/2) - (M2 - 2 mu M1 + mu^2 M0) / (2 s^2),
 //     exact algebra; the sums are streamed ONCE per data split (f64), so a step
 //     costs O(B F) instead of O(B T F).  Gradients are closed-form too.
 #include <algorithm>
@@ -375,8 +375,9 @@ __device__ __forceinline__ void key_feature(const GaussArgs& g, int k, int f, in
   }
 }
 
-// lp[k][b] = sum_f M0 (-log s - log(2 pi)/2) - (M2 - 2 mu M1 + mu^2 M0)/(2 s^2)
-// (losses.py:25-33); one block per (b, key), f64 accumulation, fixed order.
+// lp[k][b] = sum_f M0 (-log |s| - log(2 pi)/2) - (M2 - 2 mu M1 + mu^2 M0)/(2 s^2)
+// (losses.py:25-33: log(1 / sqrt(2 pi s^2)), the same for either sign of s);
+// one block per (b, key), f64 accumulation, fixed order.
 __global__ __launch_bounds__(256) void gauss_loglik_kernel(GaussArgs g, float* __restrict__ lp) {
   __shared__ double s_red[4];
   const int64_t b = blockIdx.x;
@@ -392,7 +393,7 @@ __global__ __launch_bounds__(256) void gauss_loglik_kernel(GaussArgs g, float* _
     const double m0 = st[ff], m1 = st[g.Fm[mod] + ff], m2 = st[2 * g.Fm[mod] + ff];
     const double mu = g.mu[k][b * g.ldm[k] + f], s = g.sigma[k][b * g.lds[k] + f];
     const double q = m2 - 2.0 * mu * m1 + mu * mu * m0;
-    acc += m0 * (-log(s) - hl2pi) - q / (2.0 * s * s);
+    acc += m0 * (-log(fabs(s)) - hl2pi) - q / (2.0 * s * s);
   }
   acc = wave_sum(acc);
   if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = acc;
@@ -496,8 +497,9 @@ extern "C" int mmb_word_logprob_backward(const float* latents, int64_t b, int d,
 
 extern "C" int mmb_gauss_stats(const float* x, const float* mask, int64_t n, int t, int f,
                                double* stats, hipStream_t stream) {
-  MMB_REQUIRE(x && stats && n >= 0 && t >= 0 && f > 0);
-  if (n == 0) return MMB_OK;
+  MMB_REQUIRE(n >= 0 && t >= 0 && f > 0);
+  if (n == 0) return MMB_OK;  // (empty tensors hand over null pointers)
+  MMB_REQUIRE(stats && (x || t == 0));  // t = 0: zeros, x is not read
   const int grid = static_cast<int>(std::min<int64_t>(ceil_div(n * f, 256), 256 * 16));
   gauss_stats_kernel<<<grid, 256, 0, stream>>>(x, mask, n, t, f, stats);
   MMB_LAUNCH_CHECK();
@@ -517,7 +519,7 @@ static int gauss_args(GaussArgs& g, const double* const* stats, const int* fm, c
   for (int k = 0; k < nkeys; ++k) {
     MMB_REQUIRE(mods[k] > 0 && mods[k] < 8);
     for (int m = 0; m < 3; ++m)
-      if (mods[k] >> m & 1) MMB_REQUIRE(stats[m] && fm[m] > 0);
+      if (mods[k] >> m & 1) MMB_REQUIRE(fm[m] > 0 && (stats[m] || b == 0));
     g.mods[k] = mods[k];
   }
   return MMB_OK;
@@ -545,9 +547,9 @@ extern "C" int mmb_gauss_loglik_strided(const double* const* stats, const int* f
   int rc = gauss_args(g, stats, fm, idx, b, nkeys, mods);
   if (rc != MMB_OK) return rc;
   if ((rc = gauss_strides(g, ld_mu, ld_sigma)) != MMB_OK) return rc;
-  MMB_REQUIRE(mu && sigma && lp);
+  MMB_REQUIRE(mu && sigma && (lp || b == 0));
   for (int k = 0; k < nkeys; ++k) {
-    MMB_REQUIRE(mu[k] && sigma[k]);
+    MMB_REQUIRE((mu[k] && sigma[k]) || b == 0);  // (b = 0: empty tensors, null rows)
     g.mu[k] = mu[k];
     g.sigma[k] = sigma[k];
   }
@@ -575,9 +577,9 @@ extern "C" int mmb_gauss_backward_strided(const double* const* stats, const int*
   int rc = gauss_args(g, stats, fm, idx, b, nkeys, mods);
   if (rc != MMB_OK) return rc;
   if ((rc = gauss_strides(g, ld_mu, ld_sigma)) != MMB_OK) return rc;
-  MMB_REQUIRE(mu && sigma && dlp && dmu && dsigma);
+  MMB_REQUIRE(mu && sigma && (dlp || b == 0) && dmu && dsigma);
   for (int k = 0; k < nkeys; ++k) {
-    MMB_REQUIRE(mu[k] && sigma[k]);
+    MMB_REQUIRE((mu[k] && sigma[k]) || b == 0);
     g.mu[k] = mu[k];
     g.sigma[k] = sigma[k];
     g.dmu[k] = dmu[k];

@@ -8,6 +8,10 @@ Tolerances (fp32 arithmetic on both sides, different summation order):
   CLI run           pre/embed.bin (SIF) row-relative 1e-5; post/embed.bin
                     row-relative 1e-3 after the optimisation epochs; loss
                     files 1e-4 relative; regressor MAE 1e-3 relative.
+
+The Gaussian and LayerNorm kernels against float64, at bars derived from each
+case's terms, over widths, masks, key sets, strides and offsets:
+tests/test_gpu_gauss.py.
 """
 import copy
 import json
