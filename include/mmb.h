@@ -333,6 +333,33 @@ int mmb_mm2_stream_project(const int32_t* ids, const float* table, int64_t v,
                            float* aux_out, float* mmb2_out, int32_t* flag, uint32_t* colmax,
                            void* colmax_ws, hipStream_t stream);
 
+/* mmb_mm2_stream_project on audio / visual frames of storage type frame_type
+ * (MMB_FRAMES_*, as mmb_mm2_stream_ft).  Text is gathered (ids + table,
+ * weights from wtab32 or per token from w_dense); both frame tensors, [n,t,a]
+ * and [n,t,vd] contiguous, hold elements of frame_type.  A 16-bit column unit
+ * of 4 values is one 8-byte (non-temporal) load and stays packed until its
+ * frame is summed; the widening to f32 there is exact for both 16-bit types,
+ * fp16 subnormals included, and the sums are the statements of the f32 kernel
+ * in their order: every output -- x, the three aux planes, the MMB2 rows, the
+ * column bounds and the flag word -- is bit for bit what
+ * mmb_mm2_stream_project writes for the same frames upcast to f32 by the
+ * caller.  The library rounds nothing: the caller chose the 16-bit values.
+ * Shapes, outputs, layouts, the empty call (n == 0) and the flag bits are
+ * mmb_mm2_stream_project's; like it the call never synchronises, never
+ * allocates and can be captured into a graph.
+ * MMB_FRAMES_F32 is mmb_mm2_stream_project itself for the same arguments.
+ * MMB_EINVAL before any launch: a frame_type outside 0..2, null ids, a 16-bit
+ * frame base that is not 8-byte aligned (table / num_out / wpieces stay
+ * 16-byte aligned), anything mmb_mm2_stream_project rejects.
+ * replaces: the frame loops and projections of sif2.estimate_embedding_overall_gpu2
+ *   /root/reference/sif2.py:164-208 (which reads f32 frames only)            */
+int mmb_mm2_stream_project_ft(const int32_t* ids, const float* table, int64_t v,
+                              const float* wtab32, const float* w_dense, const void* audio,
+                              const void* visual, int frame_type, int64_t n, int t, int d, int a,
+                              int vd, const void* wpieces, const float* c0, float* num_out,
+                              float* aux_out, float* mmb2_out, int32_t* flag, uint32_t* colmax,
+                              void* colmax_ws, hipStream_t stream);
+
 /* mmb_mm2_project_x3_rmpc for a few rows (the dataset splits: 100-1,284
  * rows put one or a few workgroups through the whole K loop), split over K:
  * slices (0: mmb_mm2_project_x3_split_slices) workgroups per 128-row tile

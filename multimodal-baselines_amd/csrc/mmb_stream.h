@@ -1,5 +1,5 @@
-// What the stream sources share (sif_kernels.hip, fused_kernels.hip,
-// narrow_fused_kernels.hip; included by them only): the
+// What the stream sources share (sif_kernels.hip, narrow_fused_kernels.hip
+// and, through mmb_fused.h, the three fused sources; included by them only): the
 // kernels' argument block and limits, the frame element types, the device
 // helpers more than one kernel family uses, and the declarations of the entry
 // points' host-side front end (defined once, in sif_kernels.hip).  No

@@ -8,8 +8,12 @@ the f32 ones rounded; they live beside them in HBM):
                     projection kernel at wide frames, the narrow fused kernel
                     at MOSI widths)
     f32_two_kernel  stream kernel -> s in HBM -> projection, f32 frames
-    bf16, f16       the step on 16-bit frames (always the two-kernel step:
-                    mmb_mm2_stream_ft)
+    bf16, f16       the step on 16-bit frames (the default: the two-kernel
+                    step, mmb_mm2_stream_ft)
+    bf16_fused, f16_fused
+                    the step on the same 16-bit frames with fused_frames16=True
+                    (the fused stream + projection kernel where the f32 plan
+                    takes it, mmb_mm2_stream_project_ft)
 
 Per-phase HIP event times, median per variant; for the front kernel of every
 variant its algorithmic HBM bytes per utterance (rows read once,
@@ -87,6 +91,8 @@ def main():
              "f32_two_kernel": P.FusedStep(inp, nets, stream_project=False, narrow_fused=False),
              "bf16": P.FusedStep(to_kind(inp, torch.bfloat16), nets),
              "f16": P.FusedStep(to_kind(inp, torch.float16), nets)}
+    for k in ("bf16", "f16"):  # the same 16-bit frames, opted in to the fused front
+        steps[k + "_fused"] = P.FusedStep(steps[k].inp, nets, fused_frames16=True)
     knob = {k: None for k in steps}
     for u in args.unr:  # the same steps (and buffers), launched at another depth
         for k in ("bf16", "f16"):
@@ -114,12 +120,16 @@ def main():
               f"frames {st.plan.frames}", flush=True)
     # what the rounding costs here: the 16-bit steps' rows against the f32 two-kernel step's
     ref = steps["f32_two_kernel"]
-    for k in ("bf16", "f16"):
+    for k in ("bf16", "f16", "bf16_fused", "f16_fused"):
         st = steps[k]
         run(k)
-        rel =((st.mmb2 - ref.mmb2).abs().amax(1) / ref.mmb2.abs().amax(1)).max().item()
+        rel = ((st.mmb2 - ref.mmb2).abs().amax(1) / ref.mmb2.abs().amax(1)).max().item()
         print(f"{k}: x equal to f32 {torch.equal(st.x, ref.x)}; MMB2 rows move by {rel:.2e} row-relative "
               f"(the frames' rounding)", flush=True)
+        if k.endswith("_fused"):  # against the two-kernel step on the same frames: the projection's sum order
+            two = steps[k[:-len("_fused")]]
+            rel = ((st.mmb2 - two.mmb2).abs().amax(1) / two.mmb2.abs().amax(1)).max().item()
+            print(f"{k}: against the {two.plan.frames} two-kernel step {rel:.2e} row-relative", flush=True)
     res = {k: {} for k in steps}
     for r in range(args.rounds):
         for k, st in steps.items():
