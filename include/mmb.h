@@ -479,6 +479,36 @@ int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* table, int64_
                                   float* aux_out, float* mmb2_out, int32_t* flag, uint32_t* colmax,
                                   void* colmax_ws, hipStream_t stream);
 
+/* mmb_mm2_stream_project_narrow on audio / visual frames of storage type
+ * frame_type (MMB_FRAMES_*, as mmb_mm2_stream_ft); both frame tensors,
+ * [n,t,a] and [n,t,vd] contiguous, hold elements of frame_type.  A frame
+ * instruction keeps its lane mapping (several frame rows per load, a column
+ * unit of 4 values per lane); a 16-bit unit is one 8-byte (non-temporal) load
+ * and stays packed until its frame is summed.  The widening to f32 there is
+ * exact for both 16-bit types, fp16 subnormals included, and the sums are the
+ * statements of the f32 kernel in their order: every output -- x, the three
+ * aux planes, the MMB2 rows, the column bounds and the flag word -- is bit
+ * for bit what mmb_mm2_stream_project_narrow writes for the same frames
+ * upcast to f32 by the caller.  The library rounds nothing: the caller chose
+ * the 16-bit values.  Shapes (mmb_mm2_stream_project_narrow_supported),
+ * outputs, layouts, the empty call (n == 0) and the flag bits are
+ * mmb_mm2_stream_project_narrow's; like it the call never synchronises, never
+ * allocates and can be captured into a graph.
+ * MMB_FRAMES_F32 is mmb_mm2_stream_project_narrow itself for the same
+ * arguments.
+ * MMB_EINVAL before any launch, every output untouched: a frame_type outside
+ * 0..2, a 16-bit frame base that is not 8-byte aligned (table, text cache,
+ * num_out, mmb2_out and wpieces stay 16-byte aligned), anything
+ * mmb_mm2_stream_project_narrow rejects.
+ * replaces: sif2.calc_weights + estimate_embedding_overall_gpu2
+ *   /root/reference/sif2.py:103-114,164-208 (which reads f32 frames only)    */
+int mmb_mm2_stream_project_narrow_ft(const int32_t* ids, const float* table, int64_t v,
+                                     const float* wtab32, const void* text_cache, const void* audio,
+                                     const void* visual, int frame_type, int64_t n, int t, int d,
+                                     int a, int vd, const void* wpieces, const float* c0,
+                                     float* num_out, float* aux_out, float* mmb2_out, int32_t* flag,
+                                     uint32_t* colmax, void* colmax_ws, hipStream_t stream);
+
 /* ---------------------------------------------------------------- a10/a11
  * SentimentModel(d -> h -> o): y = squeeze(W2 relu(W1 x + b1) + b2).
  * Forward for rows idx[0..b) (idx nullable = 0..b) of latents [*, d].

@@ -1,5 +1,6 @@
 // The MMB2 stream and its projection in one kernel at narrow frame widths:
-// utt_narrow_fused_kernel and mmb_mm2_stream_project_narrow.
+// utt_narrow_fused_kernel (f32, fp16 and bf16 frames), mmb_mm2_stream_project_narrow
+// and mmb_mm2_stream_project_narrow_ft.
 #include "mmb_stream.h"
 
 namespace mmb {
@@ -74,7 +75,13 @@ struct NarrowFusedArgs {
 // each per SIMD) run batches of 4 rpw rows on their own LDS halves with
 // their own (LDS counter) barriers, so that one team's batch GEMM and
 // epilogue can run beside the other team's stream phase.
-template <int UNR, int HU, int GA_MAX, int GV_MAX, bool TM = false>
+// FE: the audio / visual frames' element type (mmb_stream.h).  On 16-bit rows
+// a frame instruction keeps its lane mapping (lane = f U + c: row f of the
+// group, column unit c of 4 values) and loads the unit as 8 bytes instead of
+// 16, every byte quantity scaled by sizeof(FE); the units stay packed until
+// the frame is summed, and are widened (exactly) in front of the f32
+// instantiation's add4 / sq4.  Nothing else depends on FE.
+template <int UNR, int HU, int GA_MAX, int GV_MAX, bool TM = false, class FE = float>
 __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFWaves / 4, kNFWaves / 4))) void utt_narrow_fused_kernel(
     NarrowFusedArgs f) {
   static_assert(kNFWaves == 8, "teams of 4 waves: 8-wave workgroups");
@@ -138,8 +145,9 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
     hu[c] = 4 * min(u, NU - 1);
   }
   const bool e1 = kWave + lane < UT;  // slot 1 holds an E unit on this lane
-  const int voa = ((lane / UA) * a.A + 4 * (lane % UA)) * 4;
-  const int vov = ((lane / UV) * a.Vd + 4 * (lane % UV)) * 4;
+  constexpr int kFB = static_cast<int>(sizeof(FE));  // bytes of a frame value
+  const int voa = ((lane / UA) * a.A + 4 * (lane % UA)) * kFB;
+  const int vov = ((lane / UV) * a.Vd + 4 * (lane % UV)) * kFB;
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
   float4 cmx[CT];
 #pragma unroll
@@ -231,8 +239,8 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
   auto frame_rsrc = [&](int i, const float* base, int W) {
     const bool live = i < N;
     const int64_t ic = live ? i : 0;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + ic * L * W), 0, live ? L * W * 4 : 0,
-                                             0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<FE*>(reinterpret_cast<const FE*>(base) + ic * L * W), 0,
+                                             live ? L * W * kFB : 0, 0x00020000);
   };
   auto take = [](uint64_t& m) -> int {  // next token of a (uniform) mask, -1 = none
     const int t = m ? __builtin_ctzll(m) : -1;
@@ -271,17 +279,28 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
       float4 sa = z4, saa = z4, sv = z4, svv = z4;
       auto frames = [&](auto gmax, auto rsrc, int vo, int W, int U, int P, int g0, float4& s1, float4& s2) {
         constexpr int GM = decltype(gmax)::value;
-        float4 v[GM > 0 ? GM : 1];
+        // a group's units as loaded: a float4, or four 16-bit values packed in 8 bytes
+        std::conditional_t<kFB == 4, float4, u2> v[GM > 0 ? GM : 1];
 #pragma unroll
-        for (int g = 0; g < GM; ++g)
-          v[g] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, (g0 + g) * P * W * 4, 2));
+        for (int g = 0; g < GM; ++g) {
+          if constexpr (kFB == 4)
+            v[g] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, (g0 + g) * P * W * 4, 2));
+          else
+            v[g] = __builtin_bit_cast(u2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, vo, (g0 + g) * P * W * kFB, 2));
+        }
         const bool mine = lane < P * U;
         return [=, &s1, &s2]() {
 #pragma unroll
           for (int g = 0; g < GM; ++g) {
             if (mine) {
-              add4(s1, v[g]);
-              sq4(s2, v[g]);
+              if constexpr (kFB == 4) {
+                add4(s1, v[g]);
+                sq4(s2, v[g]);
+              } else {
+                const float4 x = frame_f32x4<FE>(v[g]);
+                add4(s1, x);
+                sq4(s2, x);
+              }
             }
           }
         };
@@ -543,6 +562,14 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
   }
 }
 
+// the product launch on 16-bit frames of type FE (mmb_mm2_stream_project_narrow_ft)
+template <class FE>
+static void launch_narrow_fused16(const NarrowFusedArgs& f, int64_t grid, hipStream_t stream) {
+  allow_dynamic_lds<&utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV, false, FE>>(kNFLds);
+  utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV, false, FE>
+      <<<static_cast<unsigned>(grid), kNFThreads, kNFLds, stream>>>(f);
+}
+
 // the narrow fused kernel's shapes: gathered ids, a weight table, 256 < d <
 // 304 (d % 4), frame rows of 4..128 floats (two or more per instruction,
 // A % 4 == Vd % 4 == 0), kq(A) + kq(Vd) <= 256, t <= 64, V <= 16384 (the
@@ -558,22 +585,30 @@ extern "C" int mmb_mm2_stream_project_narrow_supported(int t, int d, int a_, int
          v * (kNFLdq + 2) * 4 + 4 * kNFHot < (int64_t{1} << 31) && static_cast<int64_t>(t) * (a_ > vd ? a_ : vd) * 4 < (int64_t{1} << 31);
 }
 
-extern "C" int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* table, int64_t v,
-                                             const float* wtab32, const void* text_cache,
-                                             const float* audio, const float* visual, int64_t n,
-                                             int t, int d, int a_, int vd, const void* wpieces,
-                                             const float* c0, float* num_out, float* aux_out,
-                                             float* mmb2_out, int32_t* flag, uint32_t* colmax,
-                                             void* colmax_ws, hipStream_t stream) {
+// mmb_mm2_stream_project_narrow for frames of storage type frame_type
+// (MMB_FRAMES_*, validated by the caller): the checks, the text cache, the
+// rows per wave, the grid and the column bounds are the same for the three; a
+// 16-bit frame column unit is one 8-byte load, so its base is 8-byte aligned
+// where an f32 base is 16-byte aligned.
+static int narrow_project(int frame_type, const int32_t* ids, const float* table, int64_t v,
+                          const float* wtab32, const void* text_cache, const void* audio,
+                          const void* visual, int64_t n, int t, int d, int a_, int vd, const void* wpieces,
+                          const float* c0, float* num_out, float* aux_out, float* mmb2_out, int32_t* flag,
+                          uint32_t* colmax, void* colmax_ws, hipStream_t stream) {
   NarrowFusedArgs f{};
   // gathered text with the weight table only; the sums stay on chip
   MMB_REQUIRE(ids && wtab32);
-  if (const int rc = stream_args(&f.s, ids, table, v, wtab32, nullptr, nullptr, nullptr, audio, visual, n, t, d,
+  if (const int rc = stream_args(&f.s, ids, table, v, wtab32, nullptr, nullptr, nullptr,
+                                 static_cast<const float*>(audio), static_cast<const float*>(visual), n, t, d,
                                  a_, vd, num_out, nullptr, 1, aux_out, flag, colmax, colmax_ws))
     return rc;
   MMB_REQUIRE(n < (int64_t{1} << 31) - kNFRows && mmb_mm2_stream_project_narrow_supported(t, d, a_, vd, v));
   MMB_REQUIRE(text_cache && mmb2_out && wpieces && c0);
-  const StreamVec vec = stream_vec(f.s);
+  StreamVec vec = stream_vec(f.s);
+  if (frame_type != MMB_FRAMES_F32) {
+    vec.a = aligned8(audio);
+    vec.v = aligned8(visual);
+  }
   MMB_REQUIRE(vec.t && vec.a && vec.v && aligned16(text_cache) && aligned16(num_out) && aligned16(mmb2_out) &&
               aligned16(wpieces));
   if (n == 0) return empty_call(colmax, d, stream);
@@ -597,14 +632,17 @@ extern "C" int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* ta
 #ifndef MMB_HOOK_NF_TEAMS  // (tools/diag: MMB_NF_TEAMS)
 #define MMB_HOOK_NF_TEAMS 0
 #endif
-  int teams = MMB_HOOK_NF_TEAMS;  // 1: two teams of 4 waves per workgroup, 2: the same, team 1 starting a phase later
+  // 1: two teams of 4 waves per workgroup, 2: the same, team 1 starting a phase later (f32 frames)
+  int teams = frame_type == MMB_FRAMES_F32 ? MMB_HOOK_NF_TEAMS : 0;
   f.team_lag = teams == 2 ? 1 : 0;
   // batches: of 8 rpw rows, or of 4 rpw rows per team (two per workgroup)
   f.nb = ceil_div(n, static_cast<int64_t>(teams ? kNFWaves / 2 : kNFWaves) * f.rpw);
-  allow_dynamic_lds<&utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV>>(kNFLds);
+  if (frame_type == MMB_FRAMES_F32) {
+    allow_dynamic_lds<&utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV>>(kNFLds);
 #ifdef MMB_HOOK_NF_TEAMS_ATTR
-  MMB_HOOK_NF_TEAMS_ATTR;
+    MMB_HOOK_NF_TEAMS_ATTR;
 #endif
+  }
   // one workgroup per CU; the bounds: a partial row per wave
   int64_t grid = cus;
   if (colmax && grid > kCmaxRows / kNFWaves) grid = kCmaxRows / kNFWaves;
@@ -612,10 +650,38 @@ extern "C" int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* ta
 #ifndef MMB_HOOK_NF_TEAMS_LAUNCH
 #define MMB_HOOK_NF_TEAMS_LAUNCH false
 #endif
-  if (!(MMB_HOOK_NF_TEAMS_LAUNCH))
+  if (frame_type == MMB_FRAMES_F16) {
+    launch_narrow_fused16<f16_t>(f, grid, stream);
+  } else if (frame_type == MMB_FRAMES_BF16) {
+    launch_narrow_fused16<bf16_t>(f, grid, stream);
+  } else if (!(MMB_HOOK_NF_TEAMS_LAUNCH)) {
     utt_narrow_fused_kernel<kNFUnr, kNFHU, kNFGA, kNFGV><<<static_cast<unsigned>(grid), kNFThreads, kNFLds, stream>>>(f);
+  }
   MMB_LAUNCH_CHECK();
   return reduce_colmax(MMB_OK, f.s, static_cast<int>(grid) * kNFWaves, colmax, stream);
+}
+
+extern "C" int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* table, int64_t v,
+                                             const float* wtab32, const void* text_cache,
+                                             const float* audio, const float* visual, int64_t n,
+                                             int t, int d, int a_, int vd, const void* wpieces,
+                                             const float* c0, float* num_out, float* aux_out,
+                                             float* mmb2_out, int32_t* flag, uint32_t* colmax,
+                                             void* colmax_ws, hipStream_t stream) {
+  return narrow_project(MMB_FRAMES_F32, ids, table, v, wtab32, text_cache, audio, visual, n, t, d, a_, vd, wpieces,
+                        c0, num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
+}
+
+extern "C" int mmb_mm2_stream_project_narrow_ft(const int32_t* ids, const float* table, int64_t v,
+                                                const float* wtab32, const void* text_cache,
+                                                const void* audio, const void* visual, int frame_type,
+                                                int64_t n, int t, int d, int a_, int vd, const void* wpieces,
+                                                const float* c0, float* num_out, float* aux_out,
+                                                float* mmb2_out, int32_t* flag, uint32_t* colmax,
+                                                void* colmax_ws, hipStream_t stream) {
+  MMB_REQUIRE(frame_type == MMB_FRAMES_F32 || frame_type == MMB_FRAMES_F16 || frame_type == MMB_FRAMES_BF16);
+  return narrow_project(frame_type, ids, table, v, wtab32, text_cache, audio, visual, n, t, d, a_, vd, wpieces, c0,
+                        num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
 }
 
 // the tools build's two-team variant (tools/diag/); the product library

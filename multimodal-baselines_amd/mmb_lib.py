@@ -27,7 +27,8 @@ MMB_FLAG_ID_RANGE = 1
 MMB_FLAG_ZERO_WEIGHTS = 2
 MMB_FLAG_SYNC_TIMEOUT = 4
 
-# frame element types of mmb_mm2_stream_ft and mmb_mm2_stream_project_ft
+# frame element types of mmb_mm2_stream_ft, mmb_mm2_stream_project_ft and
+# mmb_mm2_stream_project_narrow_ft
 MMB_FRAMES_F32, MMB_FRAMES_F16, MMB_FRAMES_BF16 = 0, 1, 2
 
 _P = ctypes.c_void_p
@@ -86,6 +87,8 @@ SIGNATURES = {
     "mmb_mm2_stream_project_narrow_supported": (_I, [_I, _I, _I, _I, _L]),
     "mmb_mm2_stream_project_narrow": (_I, [_P, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P,
                                            _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mmb_mm2_stream_project_narrow_ft": (_I, [_P, _P, _L, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I,
+                                              _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mmb_mm2_split_bytes": (_S, [_I, _I, _I]),
     "mmb_mm2_split_pieces_bytes": (_S, [_I, _I, _I]),
     "mmb_mm2_split_pieces": (_I, [_P, _I, _I, _I, _I, _P, _P]),

@@ -625,6 +625,22 @@ def mm2_stream_project_narrow(n, t, d, a, vd, audio, visual, proj: "MMB2Projecti
     return num, aux, mmb2
 
 
+def mm2_stream_project_narrow_ft(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", ids32,
+                                 table, wtab32, flag=None, out=None, colmax=None, colmax_ws=None):
+    """mm2_stream_project_narrow on frames of any FRAME_KINDS dtype
+    (mmb_mm2_stream_project_narrow_ft): `audio` / `visual` may both be float16
+    or both bfloat16, from an 8-byte aligned base, and the outputs are bit for
+    bit those of the same frames upcast to float32.  Returns (x, aux, mmb2)."""
+    kind = frame_kind(audio, visual, "mm2_stream_project_narrow_ft")
+    proj.enable_text_cache(table, wtab32)
+    num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
+    L.call("mmb_mm2_stream_project_narrow_ft", L.ptr(ids32), L.ptr(table), table.shape[0],
+           L.ptr(wtab32), L.ptr(proj.text_cache), L.ptr(audio), L.ptr(visual), FRAME_KINDS[kind][1],
+           n, t, d, a, vd, L.ptr(proj.wpieces), L.ptr(proj.c0), L.ptr(num), L.ptr(aux), L.ptr(mmb2),
+           L.ptr(flag), L.ptr(colmax), L.ptr(colmax_ws), L.stream_ptr())
+    return num, aux, mmb2
+
+
 def mm2_stream_project(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", ids32=None,
                        table=None, wtab32=None, text_dense=None, w_dense=None, flag=None,
                        out=None, colmax=None, colmax_ws=None):
@@ -824,7 +840,7 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
               stream_project: bool | None = None, narrow_fused: bool | None = None,
               fork_projection: bool | None = None, split_stream: bool | None = None,
               split_projection: bool = True, frames: str = "f32",
-              fused_frames16: bool = False) -> StepPlan:
+              fused_frames16: bool = False, narrow_frames16: bool = False) -> StepPlan:
     """The plan of a step over `n` of a split's `n_total` utterances on a chip
     of `cus` CUs; the remaining arguments are FusedStep's overrides (None: by
     shape).  Precedence: the fused front kernels need one chunk ASKED for and
@@ -837,15 +853,21 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
     `fused_frames16` opts in to the wide-frame fused kernel on them
     (mmb_mm2_stream_project_ft): `stream_project` then keeps the caller's
     value and the front is "fused" exactly where the f32 plan of the shape
-    chooses it, "stream" everywhere else.  On f32 frames the keyword changes
-    nothing."""
+    chooses it, "stream" everywhere else.  `narrow_frames16` is its sibling
+    for the narrow fused kernel (mmb_mm2_stream_project_narrow_ft):
+    `narrow_fused` then keeps the caller's value and the front is
+    "narrow_fused" exactly where the f32 plan of the shape chooses it; with
+    both set the precedence is the f32 plan's.  On f32 frames the keywords
+    change nothing."""
     check_npc(npc)
     if frames not in FRAME_KINDS:
         raise ValueError(f"frames must be one of {', '.join(FRAME_KINDS)}, not {frames!r}")
     if frames != "f32":
-        narrow_fused = split_stream = False
+        split_stream = False
         if not fused_frames16:
             stream_project = False
+        if not narrow_frames16:
+            narrow_fused = False
     s_half = L.query("mmb_mm2_ldw", d) <= 320
     one_asked = (chunks or 1) == 1
     if stream_project is None:
@@ -900,6 +922,8 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
 # the fused front kernels: trace phase and mirror
 _FRONTS = {"fused": ("mm2_stream_project", mm2_stream_project),
            "narrow_fused": ("mm2_stream_project_narrow", mm2_stream_project_narrow)}
+# their mirrors on 16-bit frames (the same phase names)
+_FRONTS_FT = {"fused": mm2_stream_project_ft, "narrow_fused": mm2_stream_project_narrow_ft}
 
 
 class FusedStep:
@@ -949,7 +973,8 @@ class FusedStep:
     two-kernel step; `fused_frames16=True` opts in to the fused stream +
     projection kernel on them where the f32 plan of the shape would choose it
     (mm2_stream_project_ft: no s buffer, the same rows bit for bit as on the
-    upcast frames).
+    upcast frames), `narrow_frames16=True` to the narrow fused kernel in the
+    same way (mm2_stream_project_narrow_ft; MOSI's widths).
 
     Which of these a step takes is decided once, by step_plan() (`self.plan`);
     _run is one sequence over it: front kernel, chunk pipeline, projection
@@ -963,7 +988,8 @@ class FusedStep:
                  gram_kind: str | None = None, stream_project: bool | None = None,
                  narrow_fused: bool | None = None, check_each_run: bool = False,
                  fork_projection: bool | None = None, split_stream: bool | None = None,
-                 split_projection: bool = True, fused_frames16: bool = False):
+                 split_projection: bool = True, fused_frames16: bool = False,
+                 narrow_frames16: bool = False):
         self.inp = inputs
         self.check_each_run = check_each_run
         self.ids = inputs["ids"]
@@ -985,7 +1011,8 @@ class FusedStep:
                                   gram_kind=gram_kind, stream_project=stream_project,
                                   narrow_fused=narrow_fused, fork_projection=fork_projection,
                                   split_stream=split_stream, split_projection=split_projection,
-                                  frames=self.frames, fused_frames16=fused_frames16)
+                                  frames=self.frames, fused_frames16=fused_frames16,
+                                  narrow_frames16=narrow_frames16)
         self.proj = MMB2Projection(networks, self.d, self.a, self.vd, self.t, dev)
         kp = self.proj.kp
         self.x = torch.empty((self.n, self.d), dtype=torch.float32, device=dev)
@@ -1208,8 +1235,8 @@ class FusedStep:
                 self._stream_chunk(0)  # every CU
         else:
             phase, front = _FRONTS[p.front]
-            if p.frames != "f32":  # the wide-frame fused kernel on 16-bit frames (fused_frames16)
-                front = mm2_stream_project_ft
+            if p.frames != "f32":  # the fused kernels on 16-bit frames (fused_frames16 / narrow_frames16)
+                front = _FRONTS_FT[p.front]
             with mark(phase):
                 front(self.n, self.t, self.d, self.a, self.vd, self.inp["audio"],
                       self.inp["visual"], self.proj, ids32=self.ids, table=self.table,

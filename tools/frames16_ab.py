@@ -14,6 +14,10 @@ the f32 ones rounded; they live beside them in HBM):
                     the step on the same 16-bit frames with fused_frames16=True
                     (the fused stream + projection kernel where the f32 plan
                     takes it, mmb_mm2_stream_project_ft)
+    bf16_narrow, f16_narrow
+                    the same 16-bit frames with narrow_frames16=True (the
+                    narrow fused kernel where the f32 plan takes it,
+                    mmb_mm2_stream_project_narrow_ft: MOSI's widths)
 
 Per-phase HIP event times, median per variant; for the front kernel of every
 variant its algorithmic HBM bytes per utterance (rows read once,
@@ -93,6 +97,9 @@ def main():
              "f16": P.FusedStep(to_kind(inp, torch.float16), nets)}
     for k in ("bf16", "f16"):  # the same 16-bit frames, opted in to the fused front
         steps[k + "_fused"] = P.FusedStep(steps[k].inp, nets, fused_frames16=True)
+    for k in ("bf16", "f16"):  # and to the narrow fused front
+        steps[k + "_narrow"] = P.FusedStep(steps[k].inp, nets, narrow_frames16=True)
+    opted = [k for k in steps if k.endswith(("_fused", "_narrow"))]
     knob = {k: None for k in steps}
     for u in args.unr:  # the same steps (and buffers), launched at another depth
         for k in ("bf16", "f16"):
@@ -120,14 +127,14 @@ def main():
               f"frames {st.plan.frames}", flush=True)
     # what the rounding costs here: the 16-bit steps' rows against the f32 two-kernel step's
     ref = steps["f32_two_kernel"]
-    for k in ("bf16", "f16", "bf16_fused", "f16_fused"):
+    for k in ["bf16", "f16"] + opted:
         st = steps[k]
         run(k)
         rel = ((st.mmb2 - ref.mmb2).abs().amax(1) / ref.mmb2.abs().amax(1)).max().item()
         print(f"{k}: x equal to f32 {torch.equal(st.x, ref.x)}; MMB2 rows move by {rel:.2e} row-relative "
               f"(the frames' rounding)", flush=True)
-        if k.endswith("_fused"):  # against the two-kernel step on the same frames: the projection's sum order
-            two = steps[k[:-len("_fused")]]
+        if k in opted:  # against the two-kernel step on the same frames: the projection's sum order
+            two = steps[k.split("_")[0]]
             rel = ((st.mmb2 - two.mmb2).abs().amax(1) / two.mmb2.abs().amax(1)).max().item()
             print(f"{k}: against the {two.plan.frames} two-kernel step {rel:.2e} row-relative", flush=True)
     res = {k: {} for k in steps}
