@@ -17,9 +17,7 @@ static int launch_fused(const FusedArgs& f, int grid, hipStream_t stream) {
 
 // mmb_mm2_stream_project for frames of storage type frame_type
 // (MMB_FRAMES_*, validated by the caller): the checks, the launch geometry
-// and the column bounds are the same for the three; a 16-bit frame column
-// unit is one 8-byte load, so its base is 8-byte aligned where an f32 base
-// is 16-byte aligned.
+// and the column bounds are the same for the three.
 static int fused_project(int frame_type, const int32_t* ids, const float* table, int64_t v,
                          const float* wtab32, const float* text_dense, const float* w_dense,
                          const void* audio, const void* visual, int64_t n, int t, int d, int a_, int vd,
@@ -29,17 +27,13 @@ static int fused_project(int frame_type, const int32_t* ids, const float* table,
   FusedArgs f{};
   // the weighted sum's rows are the text frames themselves; the sums stay on
   // chip (no s_out), fp16 hi | lo
-  if (const int rc = stream_args(&f.s, ids, table, v, wtab32, text_dense, text_dense, w_dense,
-                                 static_cast<const float*>(audio), static_cast<const float*>(visual), n, t, d,
-                                 a_, vd, num_out, nullptr, 1, aux_out, flag, colmax, colmax_ws))
+  if (const int rc = stream_args(&f.s, ids, table, v, wtab32, text_dense, text_dense, w_dense, audio, visual, n, t,
+                                 d, a_, vd, num_out, nullptr, 1, aux_out, flag, colmax, colmax_ws))
     return rc;
   MMB_REQUIRE(mmb_mm2_stream_project_supported(t, d, a_, vd) && mmb2_out && wpieces && c0);
-  // float4 rows are required here, not an option: no scalar fused kernel
-  StreamVec vec = stream_vec(f.s);
-  if (frame_type != MMB_FRAMES_F32) {
-    vec.a = aligned8(audio);
-    vec.v = aligned8(visual);
-  }
+  // vector rows are required here, not an option: no scalar fused kernel
+  // (stream_vec's width % 4 asks nothing new: the predicate above has it)
+  const StreamVec vec = stream_vec(f.s, frame_bytes(frame_type));
   MMB_REQUIRE(vec.t && vec.a && vec.v && aligned16(num_out) && aligned16(wpieces));
   if (n == 0) return empty_call(colmax, d, stream);
   f.kq[0] = piece_k(d);
@@ -108,13 +102,8 @@ extern "C" int mmb_mm2_stream_project_ft(const int32_t* ids, const float* table,
                                          int a_, int vd, const void* wpieces, const float* c0,
                                          float* num_out, float* aux_out, float* mmb2_out, int32_t* flag,
                                          uint32_t* colmax, void* colmax_ws, hipStream_t stream) {
-  MMB_REQUIRE(frame_type == MMB_FRAMES_F32 || frame_type == MMB_FRAMES_F16 || frame_type == MMB_FRAMES_BF16);
+  MMB_REQUIRE(frame_bytes(frame_type) != 0);
   MMB_REQUIRE(ids);  // gathered text only
-  if (frame_type == MMB_FRAMES_F32) {
-    return mmb_mm2_stream_project(ids, table, v, wtab32, nullptr, w_dense, static_cast<const float*>(audio),
-                                  static_cast<const float*>(visual), n, t, d, a_, vd, wpieces, c0, num_out,
-                                  aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
-  }
   return fused_project(frame_type, ids, table, v, wtab32, nullptr, w_dense, audio, visual, n, t, d, a_, vd, wpieces,
                        c0, num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
 }

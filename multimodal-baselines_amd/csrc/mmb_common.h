@@ -137,7 +137,6 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // 16-byte alignment: what every float4 / b128 access of a row base needs
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 // K rows of one modality's piece [Sx_m | Sxx_m] (2 w sums) in the piece-
 // ordered weight image, padded to whole 32-deep chunks.  The image's writer

@@ -533,8 +533,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
             } else if (m == 0) {
               text_piece<UNR>(a, i, lane, num, sx, sxx, cnt, sw);
             } else {
-              const FE* base = m == 1 ? reinterpret_cast<const FE*>(a.audio) + i * a.L * a.A
-                                      : reinterpret_cast<const FE*>(a.visual) + i * a.L * a.Vd;
+              const FE* base = m == 1 ? frames<FE>(a.audio) + i * a.L * a.A : frames<FE>(a.visual) + i * a.L * a.Vd;
               frame_piece<UNR, NT, FE>(base, W, a.L, lane, sx, sxx);
             }
             finish_row(std::true_type{}, std::integral_constant<int, 2>{}, j, m, q, i, num[0], sx[0], sxx[0],
@@ -613,7 +612,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
         constexpr bool TAIL = ((TM >> m) & 1) != 0;
         const int W = wdt[m], UW = W >> 2;
         const int ngr = (L + UNR - 1) / UNR, ng = nrows * ngr;
-        const float* src = TEXT ? (gather ? a.table : a.text_dense) : (m == 1 ? a.audio : a.visual);
+        const void* src = TEXT ? (gather ? a.table : a.text_dense) : (m == 1 ? a.audio : a.visual);
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
         int cur = 0;                        // the row being summed
         int rid_c = -1, rid_n = -1, raw_n = -1;
@@ -642,7 +641,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
           int rid = 0;
           if constexpr (TEXT) rid = rr == cur ? rid_c : rid_n;
           const bool rowbase = !TEXT || !gather;  // frames [L][W] of row i
-          const RowE* rsrc_base = reinterpret_cast<const RowE*>(src);  // (text: never 16-bit)
+          const RowE* rsrc_base = frames<RowE>(src);  // (text: never 16-bit)
           const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(
               const_cast<RowE*>(rowbase ? rsrc_base + i * L * W : rsrc_base), 0,
               rowbase ? L * W * EB : static_cast<int>(a.V * D * 4), 0x00020000);
@@ -798,13 +797,13 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
           const int rr = NX ? 0 : g / ngr, t0 = NX ? 0 : (g - rr * ngr) * UNR;
           const int64_t i = NX ? (M == 2 ? ni0 : i0) : i0 + 4 * rr;
           const int W2 = wdt[MM], U2 = W2 >> 2;
-          const float* s2 = T2 ? (gather ? a.table : a.text_dense) : (MM == 1 ? a.audio : a.visual);
+          const void* s2 = T2 ? (gather ? a.table : a.text_dense) : (MM == 1 ? a.audio : a.visual);
           const int o0 = NX ? 4 * E2 * min(lane, U2 - 1) : vo0, o1 = NX ? E2 * min(4 * kWave + lane, W2 - 1) : vo1;
           int rid = 0;
           if constexpr (T2) rid = NX ? rid_pre : (rr == cur ? rid_c : rid_n);
           const bool rowbase = !T2 || !gather;
           using Row2 = frame_row_t<E2>;
-          const Row2* r2 = reinterpret_cast<const Row2*>(s2);  // (text: never 16-bit)
+          const Row2* r2 = frames<Row2>(s2);  // (text: never 16-bit)
           const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(
               const_cast<Row2*>(rowbase ? r2 + i * L * W2 : r2), 0,
               rowbase ? L * W2 * E2 : static_cast<int>(a.V * D * 4), 0x00020000);

@@ -25,8 +25,8 @@ struct StreamArgs {
   const float* w_dense;     // [N,L] given weights
   const float* text_dense;  // [N,L,D] dense text frames (MMB2 drop-in mode)
   const float* emb_dense;   // [N,L,D] rows for the weighted sum (may alias text_dense)
-  const float* audio;       // [N,L,A]   (elements of the kernel's frame type FE: a 16-bit
-  const float* visual;      // [N,L,Vd]   instantiation reads both through const FE*)
+  const void* audio;        // [N,L,A]   elements of the kernel's frame type FE,
+  const void* visual;       // [N,L,Vd]  read through frames<FE>()
   int64_t N;
   int L, D, A, Vd, Kp;
   float* x_out;
@@ -70,6 +70,15 @@ struct bf16_t {          // bfloat16: the high half of an f32
   uint16_t bits;
 };
 using u2 = unsigned __attribute__((ext_vector_type(2)));  // four 16-bit frame values
+// StreamArgs::audio / ::visual as the frames of type FE they hold
+template <class FE>
+__device__ __forceinline__ const FE* frames(const void* p) {
+  return static_cast<const FE*>(p);
+}
+// bytes of a frame value of storage type frame_type (MMB_FRAMES_*, include/mmb.h); 0: not a frame type
+inline int frame_bytes(int frame_type) {
+  return frame_type == MMB_FRAMES_F32 ? 4 : (frame_type == MMB_FRAMES_F16 || frame_type == MMB_FRAMES_BF16) ? 2 : 0;
+}
 template <class FE>
 __device__ __forceinline__ float frame_f32(uint32_t bits16) {
   if constexpr (std::is_same_v<FE, bf16_t>) {
@@ -289,17 +298,18 @@ bool set_text_source(StreamArgs* s, const int32_t* ids, const float* table, int6
                      const float* wtab32, const float* text_dense, const float* emb_dense,
                      const float* w_dense);
 int stream_args(StreamArgs* s, const int32_t* ids, const float* table, int64_t v, const float* wtab32,
-                const float* text_dense, const float* emb_dense, const float* w_dense, const float* audio,
-                const float* visual, int64_t n, int t, int d, int a_, int vd, float* num_out, void* s_out,
+                const float* text_dense, const float* emb_dense, const float* w_dense, const void* audio,
+                const void* visual, int64_t n, int t, int d, int a_, int vd, float* num_out, void* s_out,
                 int s_half, float* aux_out, int32_t* flag, const uint32_t* colmax, void* colmax_ws);
 int empty_call(uint32_t* colmax, int d, hipStream_t stream);
 int reduce_colmax(int rc, const StreamArgs& s, int parts, uint32_t* colmax, hipStream_t stream);
-// float4 eligibility of the three modalities: rows of whole float4 units from
-// a 16-byte aligned base
+// vector eligibility of the three modalities: rows of whole 4-value column
+// units from a base aligned to one unit -- 16 bytes of text, 4 * fbytes
+// (frame_bytes) of audio / visual
 struct StreamVec {
   bool t, a, v;
 };
-StreamVec stream_vec(const StreamArgs& s);
+StreamVec stream_vec(const StreamArgs& s, int fbytes = 4);
 bool units_fit(const StreamArgs& s, const StreamVec& vec);
 #pragma GCC visibility pop
 

@@ -236,10 +236,10 @@ __global__ __launch_bounds__(kNFThreads) __attribute__((amdgpu_waves_per_eu(kNFW
     }
   };
 
-  auto frame_rsrc = [&](int i, const float* base, int W) {
+  auto frame_rsrc = [&](int i, const void* base, int W) {
     const bool live = i < N;
     const int64_t ic = live ? i : 0;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<FE*>(reinterpret_cast<const FE*>(base) + ic * L * W), 0,
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<FE*>(frames<FE>(base) + ic * L * W), 0,
                                              live ? L * W * kFB : 0, 0x00020000);
   };
   auto take = [](uint64_t& m) -> int {  // next token of a (uniform) mask, -1 = none
@@ -587,9 +587,7 @@ extern "C" int mmb_mm2_stream_project_narrow_supported(int t, int d, int a_, int
 
 // mmb_mm2_stream_project_narrow for frames of storage type frame_type
 // (MMB_FRAMES_*, validated by the caller): the checks, the text cache, the
-// rows per wave, the grid and the column bounds are the same for the three; a
-// 16-bit frame column unit is one 8-byte load, so its base is 8-byte aligned
-// where an f32 base is 16-byte aligned.
+// rows per wave, the grid and the column bounds are the same for the three.
 static int narrow_project(int frame_type, const int32_t* ids, const float* table, int64_t v,
                           const float* wtab32, const void* text_cache, const void* audio,
                           const void* visual, int64_t n, int t, int d, int a_, int vd, const void* wpieces,
@@ -598,17 +596,13 @@ static int narrow_project(int frame_type, const int32_t* ids, const float* table
   NarrowFusedArgs f{};
   // gathered text with the weight table only; the sums stay on chip
   MMB_REQUIRE(ids && wtab32);
-  if (const int rc = stream_args(&f.s, ids, table, v, wtab32, nullptr, nullptr, nullptr,
-                                 static_cast<const float*>(audio), static_cast<const float*>(visual), n, t, d,
+  if (const int rc = stream_args(&f.s, ids, table, v, wtab32, nullptr, nullptr, nullptr, audio, visual, n, t, d,
                                  a_, vd, num_out, nullptr, 1, aux_out, flag, colmax, colmax_ws))
     return rc;
   MMB_REQUIRE(n < (int64_t{1} << 31) - kNFRows && mmb_mm2_stream_project_narrow_supported(t, d, a_, vd, v));
   MMB_REQUIRE(text_cache && mmb2_out && wpieces && c0);
-  StreamVec vec = stream_vec(f.s);
-  if (frame_type != MMB_FRAMES_F32) {
-    vec.a = aligned8(audio);
-    vec.v = aligned8(visual);
-  }
+  // (stream_vec's width % 4 asks nothing new: the predicate above has it)
+  const StreamVec vec = stream_vec(f.s, frame_bytes(frame_type));
   MMB_REQUIRE(vec.t && vec.a && vec.v && aligned16(text_cache) && aligned16(num_out) && aligned16(mmb2_out) &&
               aligned16(wpieces));
   if (n == 0) return empty_call(colmax, d, stream);
@@ -679,7 +673,7 @@ extern "C" int mmb_mm2_stream_project_narrow_ft(const int32_t* ids, const float*
                                                 const float* c0, float* num_out, float* aux_out,
                                                 float* mmb2_out, int32_t* flag, uint32_t* colmax,
                                                 void* colmax_ws, hipStream_t stream) {
-  MMB_REQUIRE(frame_type == MMB_FRAMES_F32 || frame_type == MMB_FRAMES_F16 || frame_type == MMB_FRAMES_BF16);
+  MMB_REQUIRE(frame_bytes(frame_type) != 0);
   return narrow_project(frame_type, ids, table, v, wtab32, text_cache, audio, visual, n, t, d, a_, vd, wpieces, c0,
                         num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
 }

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(NT) void utt_stream_kernel(StreamArgs a) {
     for (int e = 0; e < VV; ++e) sv[e] = svv[e] = 0.f;
     if constexpr (MM2) {
       if (rA < RA) {
-        const FE* base = reinterpret_cast<const FE*>(a.audio) + (i * a.L) * a.A + cA * VA;
+        const FE* base = frames<FE>(a.audio) + (i * a.L) * a.A + cA * VA;
 #pragma unroll FU
         for (int t = rA; t < a.L; t += RA) {
           float v[VA];
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(NT) void utt_stream_kernel(StreamArgs a) {
         }
       }
       if (rV < RV) {
-        const FE* base = reinterpret_cast<const FE*>(a.visual) + (i * a.L) * a.Vd + cV * VV;
+        const FE* base = frames<FE>(a.visual) + (i * a.L) * a.Vd + cV * VV;
 #pragma unroll FU
         for (int t = rV; t < a.L; t += RV) {
           float v[VV];
@@ -495,9 +495,9 @@ __global__ __launch_bounds__(kNT) void utt_split_part_kernel(StreamArgs a, Split
     }
   };
   if (vis)
-    stream(a.visual, a.Vd, prow + 2 * a.A, std::integral_constant<int, VV>{});
+    stream(frames<float>(a.visual), a.Vd, prow + 2 * a.A, std::integral_constant<int, VV>{});
   else
-    stream(a.audio, a.A, prow, std::integral_constant<int, VA>{});
+    stream(frames<float>(a.audio), a.A, prow, std::integral_constant<int, VA>{});
 }
 
 // The partials of utterance i (blockIdx.x) in part order, then the row's
@@ -686,8 +686,8 @@ __device__ __forceinline__ void utt_sums(const StreamArgs& a, int64_t i, int lan
   for (int c = 0; c < CA; ++c) sa[c] = saa[c] = z4;
 #pragma unroll
   for (int c = 0; c < CV; ++c) sv[c] = svv[c] = z4;
-  const FE* abase = reinterpret_cast<const FE*>(a.audio) + i * a.L * a.A;
-  const FE* vbase = reinterpret_cast<const FE*>(a.visual) + i * a.L * a.Vd;
+  const FE* abase = frames<FE>(a.audio) + i * a.L * a.A;
+  const FE* vbase = frames<FE>(a.visual) + i * a.L * a.Vd;
   const int64_t dbase = i * a.L;
   // Column offsets clamped into the row so every lane loads unconditionally:
   // lanes past a row's width read a valid duplicate and never store it.  A
@@ -978,9 +978,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
 
     // frames: the first GA_MAX / GV_MAX packed instructions per modality
     // issued before the text loop (rows past L read zeros past the record count)
-    const auto arsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.audio + i * L * a.A), 0,
+    const auto arsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(frames<float>(a.audio) + i * L * a.A), 0,
                                                          L * a.A * 4, 0x00020000);
-    const auto vrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.visual + i * L * a.Vd), 0,
+    const auto vrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(frames<float>(a.visual) + i * L * a.Vd), 0,
                                                          L * a.Vd * 4, 0x00020000);
     float4 sa = z4, saa = z4, sv = z4, svv = z4;
     auto frames = [&](auto gmax, auto rsrc, int vo, int W, int U, int P, int g0, float4& s1, float4& s2) {
@@ -1360,9 +1360,9 @@ static int launch_stream(const StreamArgs& a, hipStream_t stream, int* parts = n
 }
 
 // ------------------------------------------------ the entry points' front end
-// What mmb_sif_wavg and the four MMB2 stream entry points do alike, once:
+// What mmb_sif_wavg and the MMB2 stream entry points do alike, once:
 // their shared checks and the StreamArgs they hand to a kernel, the empty
-// call, the float4 eligibility of the three modalities, and the column-bound
+// call, the vector eligibility of the three modalities, and the column-bound
 // reduction that ends every path.  An entry point keeps what is particular to
 // it: its own limits, its kernel choice and its grid.
 
@@ -1381,8 +1381,8 @@ bool set_text_source(StreamArgs* s, const int32_t* ids, const float* table, int6
 // which keep the sums on chip), after the checks every such call gets:
 // positive shapes, the text source, the outputs, bounds only with a workspace.
 int stream_args(StreamArgs* s, const int32_t* ids, const float* table, int64_t v, const float* wtab32,
-                const float* text_dense, const float* emb_dense, const float* w_dense, const float* audio,
-                const float* visual, int64_t n, int t, int d, int a_, int vd, float* num_out, void* s_out,
+                const float* text_dense, const float* emb_dense, const float* w_dense, const void* audio,
+                const void* visual, int64_t n, int t, int d, int a_, int vd, float* num_out, void* s_out,
                 int s_half, float* aux_out, int32_t* flag, const uint32_t* colmax, void* colmax_ws) {
   MMB_REQUIRE(n >= 0 && t > 0 && d > 0 && a_ > 0 && vd > 0);
   MMB_REQUIRE(audio && visual && num_out && aux_out && (s_half == 0 || s_half == 1));
@@ -1413,11 +1413,16 @@ int reduce_colmax(int rc, const StreamArgs& s, int parts, uint32_t* colmax, hipS
   return MMB_OK;
 }
 
-// float4 eligibility of the three modalities (StreamVec): rows of whole
-// float4 units from a 16-byte aligned base
-StreamVec stream_vec(const StreamArgs& s) {
+// Vector eligibility of the three modalities (StreamVec): rows of whole
+// column units of 4 values from a base aligned to one unit.  A text unit is a
+// float4; a frame unit is 4 * fbytes bytes (frame_bytes: 16 of f32, one b128
+// load, 8 of a 16-bit type, one b64 load).
+StreamVec stream_vec(const StreamArgs& s, int fbytes) {
+  auto unit = [&](int w, const void* p) {
+    return w % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & (4 * fbytes - 1)) == 0;
+  };
   return {s.D % 4 == 0 && (s.ids ? aligned16(s.table) : (aligned16(s.text_dense) && aligned16(s.emb_dense))),
-          s.A % 4 == 0 && aligned16(s.audio), s.Vd % 4 == 0 && aligned16(s.visual)};
+          unit(s.A, s.audio), unit(s.Vd, s.visual)};
 }
 // the workgroup kernels' limit: a thread per column unit (float4 or scalar)
 bool units_fit(const StreamArgs& s, const StreamVec& vec) {
@@ -1525,53 +1530,18 @@ extern "C" size_t mmb_mm2_colmax_ws_bytes(int d) {
   return static_cast<size_t>(kCmaxRows) * (d > 0 ? d : 0) * sizeof(float) + 16;
 }
 
-extern "C" int mmb_mm2_stream(const int32_t* ids, const float* table, int64_t v,
-                              const float* wtab32, const float* text_dense,
-                              const float* emb_dense, const float* w_dense, const float* audio,
-                              const float* visual, int64_t n, int t, int d, int a_, int vd,
-                              float* num_out, void* s_out, int s_half, float* aux_out,
-                              int32_t* flag, uint32_t* colmax, void* colmax_ws,
-                              hipStream_t stream) {
-  StreamArgs s;
-  if (const int rc = stream_args(&s, ids, table, v, wtab32, text_dense, emb_dense, w_dense, audio, visual, n,
-                                 t, d, a_, vd, num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws))
-    return rc;
-  MMB_REQUIRE(s_out && (colmax == nullptr || d <= 2 * kNT));
-  if (n == 0) return empty_call(colmax, d, stream);
+// The routes of mmb_mm2_stream and mmb_mm2_stream_ft on frames of type FE,
+// after the entry point's checks: the wave kernel where every modality and
+// both outputs take vector rows, else the workgroup kernel (and the pass that
+// makes its fp32 sums fp16 hi | lo); then the column bounds.
+template <class FE>
+static int stream_route(StreamArgs& s, uint32_t* colmax, hipStream_t stream) {
   int parts = 0;
-  const StreamVec vec = stream_vec(s);
-  // the wave kernel: float4 rows of every modality and of both outputs, at
+  const int s_half = s.s_half;
+  const StreamVec vec = stream_vec(s, sizeof(FE));
+  // the wave kernel: vector rows of every modality and of both outputs, at
   // most 64 tokens and 512 columns; anything else is not rejected but falls
   // through to the workgroup kernel
-  if (vec.t && vec.a && vec.v && t <= kWave && d <= 512 && a_ <= 512 && vd <= 512 && aligned16(num_out) &&
-      aligned16(s_out)) {
-    const int rc = dispatch3(d > 256, a_ > 256, vd > 256, [&](auto ct, auto ca, auto cv) {
-      return launch_wave<true, ct.value ? 2 : 1, ca.value ? 2 : 1, cv.value ? 2 : 1>(s, stream, &parts);
-    });
-    return reduce_colmax(rc, s, parts, colmax, stream);
-  }
-  MMB_REQUIRE(units_fit(s, vec));
-  s.s_half = 0;  // fp32 sums; split_rows_kernel makes them fp16 hi | lo afterwards
-  int rc = dispatch3(vec.t, vec.a, vec.v, [&](auto vt, auto va, auto vv) {
-    return launch_stream<true, vt.value ? 4 : 1, va.value ? 4 : 1, vv.value ? 4 : 1>(s, stream, &parts);
-  });
-  rc = reduce_colmax(rc, s, parts, colmax, stream);
-  if (rc != MMB_OK || !s_half) return rc;
-  split_rows_kernel<<<static_cast<unsigned>(n), 256, s.Kp * sizeof(float), stream>>>(
-      s.s_out, aux_out + 2 * n, s.Kp);
-  MMB_LAUNCH_CHECK();
-  return MMB_OK;
-}
-
-// mmb_mm2_stream's two routes on 16-bit frames of type FE.  A frame column
-// unit is still 4 values, now 8 bytes: a modality is vector-eligible from an
-// 8-byte aligned base.
-template <class FE>
-static int stream_frames16(StreamArgs& s, int s_half, float* aux_out, uint32_t* colmax, hipStream_t stream) {
-  int parts = 0;
-  StreamVec vec = stream_vec(s);
-  vec.a = s.A % 4 == 0 && aligned8(s.audio);
-  vec.v = s.Vd % 4 == 0 && aligned8(s.visual);
   if (vec.t && vec.a && vec.v && s.L <= kWave && s.D <= 512 && s.A <= 512 && s.Vd <= 512 &&
       aligned16(s.num_out) && aligned16(s.s_out)) {
     const int rc = dispatch3(s.D > 256, s.A > 256, s.Vd > 256, [&](auto ct, auto ca, auto cv) {
@@ -1586,10 +1556,26 @@ static int stream_frames16(StreamArgs& s, int s_half, float* aux_out, uint32_t* 
   });
   rc = reduce_colmax(rc, s, parts, colmax, stream);
   if (rc != MMB_OK || !s_half) return rc;
-  split_rows_kernel<<<static_cast<unsigned>(s.N), 256, s.Kp * sizeof(float), stream>>>(s.s_out, aux_out + 2 * s.N,
-                                                                                      s.Kp);
+  split_rows_kernel<<<static_cast<unsigned>(s.N), 256, s.Kp * sizeof(float), stream>>>(
+      s.s_out, s.aux_out + 2 * s.N, s.Kp);
   MMB_LAUNCH_CHECK();
   return MMB_OK;
+}
+
+extern "C" int mmb_mm2_stream(const int32_t* ids, const float* table, int64_t v,
+                              const float* wtab32, const float* text_dense,
+                              const float* emb_dense, const float* w_dense, const float* audio,
+                              const float* visual, int64_t n, int t, int d, int a_, int vd,
+                              float* num_out, void* s_out, int s_half, float* aux_out,
+                              int32_t* flag, uint32_t* colmax, void* colmax_ws,
+                              hipStream_t stream) {
+  StreamArgs s;
+  if (const int rc = stream_args(&s, ids, table, v, wtab32, text_dense, emb_dense, w_dense, audio, visual, n,
+                                 t, d, a_, vd, num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws))
+    return rc;
+  MMB_REQUIRE(s_out && (colmax == nullptr || d <= 2 * kNT));
+  if (n == 0) return empty_call(colmax, d, stream);
+  return stream_route<float>(s, colmax, stream);
 }
 
 extern "C" int mmb_mm2_stream_ft(const int32_t* ids, const float* table, int64_t v, const float* wtab32,
@@ -1597,23 +1583,20 @@ extern "C" int mmb_mm2_stream_ft(const int32_t* ids, const float* table, int64_t
                                  int64_t n, int t, int d, int a_, int vd, float* num_out, void* s_out,
                                  int s_half, float* aux_out, int32_t* flag, uint32_t* colmax,
                                  void* colmax_ws, hipStream_t stream) {
-  MMB_REQUIRE(frame_type == MMB_FRAMES_F32 || frame_type == MMB_FRAMES_F16 || frame_type == MMB_FRAMES_BF16);
+  const int fb = frame_bytes(frame_type);
+  MMB_REQUIRE(fb != 0);
   MMB_REQUIRE(ids);  // gathered text only
-  const float* fa = static_cast<const float*>(audio);
-  const float* fv = static_cast<const float*>(visual);
-  if (frame_type == MMB_FRAMES_F32) {
-    return mmb_mm2_stream(ids, table, v, wtab32, nullptr, nullptr, w_dense, fa, fv, n, t, d, a_, vd, num_out,
-                          s_out, s_half, aux_out, flag, colmax, colmax_ws, stream);
-  }
   StreamArgs s;
-  if (const int rc = stream_args(&s, ids, table, v, wtab32, nullptr, nullptr, w_dense, fa, fv, n, t, d, a_, vd,
-                                 num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws))
+  if (const int rc = stream_args(&s, ids, table, v, wtab32, nullptr, nullptr, w_dense, audio, visual, n, t, d,
+                                 a_, vd, num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws))
     return rc;
   MMB_REQUIRE(s_out && (colmax == nullptr || d <= 2 * kNT));
-  MMB_REQUIRE((reinterpret_cast<uintptr_t>(audio) & 1) == 0 && (reinterpret_cast<uintptr_t>(visual) & 1) == 0);
+  // a 16-bit value is never read from an odd address, scalar rows included
+  MMB_REQUIRE(fb == 4 || ((reinterpret_cast<uintptr_t>(audio) | reinterpret_cast<uintptr_t>(visual)) & 1) == 0);
   if (n == 0) return empty_call(colmax, d, stream);
-  return frame_type == MMB_FRAMES_F16 ? stream_frames16<f16_t>(s, s_half, aux_out, colmax, stream)
-                                      : stream_frames16<bf16_t>(s, s_half, aux_out, colmax, stream);
+  return frame_type == MMB_FRAMES_F32   ? stream_route<float>(s, colmax, stream)
+         : frame_type == MMB_FRAMES_F16 ? stream_route<f16_t>(s, colmax, stream)
+                                        : stream_route<bf16_t>(s, colmax, stream);
 }
 
 // Ranges per utterance of the few-long-rows path: about one workgroup per

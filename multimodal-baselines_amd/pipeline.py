@@ -511,12 +511,6 @@ def frame_kind(audio: torch.Tensor, visual: torch.Tensor, who: str = "mm2_stream
     raise L.MMBError(f"{who}: frames must be float32, float16 or bfloat16, not {audio.dtype}")
 
 
-def _require_f32_frames(audio, visual, who: str) -> None:
-    if frame_kind(audio, visual, who) != "f32":
-        raise L.MMBError(f"{who} reads float32 frames only, not {audio.dtype}: 16-bit frames "
-                         f"take mm2_stream (the two-kernel step)")
-
-
 def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=None,
                text_dense=None, emb_dense=None, w_dense=None, flag=None, out=None,
                s_half: bool = True, colmax=None, colmax_ws=None, split=None, parts: int = 0):
@@ -562,23 +556,21 @@ def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=Non
         raise L.MMBError("s buffer dtype does not match s_half")
     V = table.shape[0] if table is not None else 0
     _check_colmax_ws(colmax_ws, d)
+    # the arguments the three entry points share: the gathered text's, the
+    # frames', and everything from the shapes on
+    gathered = (L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32))
+    frames = (L.ptr(audio), L.ptr(visual))
+    tail = (n, t, d, a, vd, L.ptr(num), L.ptr(s), int(s_half), L.ptr(aux), L.ptr(flag),
+            L.ptr(colmax), L.ptr(colmax_ws))
+    text = (*gathered, L.ptr(text_dense), L.ptr(emb_dense), L.ptr(w_dense))
     if split is not None:
-        L.call("mmb_mm2_stream_split", L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32),
-               L.ptr(text_dense), L.ptr(emb_dense), L.ptr(w_dense), L.ptr(audio), L.ptr(visual),
-               n, t, d, a, vd, L.ptr(num), L.ptr(s), int(s_half), L.ptr(aux), L.ptr(flag),
-               L.ptr(colmax), L.ptr(colmax_ws), int(parts), L.ptr(split),
+        L.call("mmb_mm2_stream_split", *text, *frames, *tail, int(parts), L.ptr(split),
                split.numel() * split.element_size(), L.stream_ptr())
-        return num, s, aux
-    if kind != "f32":
-        L.call("mmb_mm2_stream_ft", L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32), L.ptr(w_dense),
-               L.ptr(audio), L.ptr(visual), FRAME_KINDS[kind][1], n, t, d, a, vd, L.ptr(num),
-               L.ptr(s), int(s_half), L.ptr(aux), L.ptr(flag), L.ptr(colmax), L.ptr(colmax_ws),
+    elif kind != "f32":
+        L.call("mmb_mm2_stream_ft", *gathered, L.ptr(w_dense), *frames, FRAME_KINDS[kind][1], *tail,
                L.stream_ptr())
-        return num, s, aux
-    L.call("mmb_mm2_stream", L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32), L.ptr(text_dense),
-           L.ptr(emb_dense), L.ptr(w_dense), L.ptr(audio), L.ptr(visual), n, t, d, a, vd,
-           L.ptr(num), L.ptr(s), int(s_half), L.ptr(aux), L.ptr(flag), L.ptr(colmax),
-           L.ptr(colmax_ws), L.stream_ptr())
+    else:
+        L.call("mmb_mm2_stream", *text, *frames, *tail, L.stream_ptr())
     return num, s, aux
 
 
@@ -611,18 +603,38 @@ def narrow_fused_supported(t: int, d: int, a: int, vd: int, v: int) -> bool:
     return bool(L.query("mmb_mm2_stream_project_narrow_supported", t, d, a, vd, v))
 
 
+def _stream_project(entry: str, ft: bool, cache: bool, text: tuple, n, t, d, a, vd, audio, visual,
+                    proj: "MMB2Projection", ids32, table, wtab32, flag, out, colmax, colmax_ws):
+    """The one body of the four fused mirrors: the call of mmb_<entry>.  `ft`:
+    the entry point takes frames of any FRAME_KINDS dtype (and their
+    frame_type), else float32 frames only; `cache`: it reads the projection's
+    text cache, else only its weight pieces; `text`: the entry point's own
+    text arguments, between wtab32 (or the text cache) and audio."""
+    kind = frame_kind(audio, visual, entry)
+    if not ft and kind != "f32":
+        raise L.MMBError(f"{entry} reads float32 frames only, not {audio.dtype}: 16-bit frames "
+                         f"take mm2_stream (the two-kernel step)")
+    if ft and not cache and ids32 is None:  # (the narrow entry points: the C side's own check)
+        raise L.MMBError(f"{entry}: gathered text (ids32 + table) only")
+    if cache:
+        proj.enable_text_cache(table, wtab32)
+    else:
+        proj.enable_pieces()
+    num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
+    V = table.shape[0] if table is not None else 0
+    L.call("mmb_" + entry, L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32),
+           *([L.ptr(proj.text_cache)] if cache else []), *map(L.ptr, text), L.ptr(audio), L.ptr(visual),
+           *([FRAME_KINDS[kind][1]] if ft else []), n, t, d, a, vd, L.ptr(proj.wpieces), L.ptr(proj.c0),
+           L.ptr(num), L.ptr(aux), L.ptr(mmb2), L.ptr(flag), L.ptr(colmax), L.ptr(colmax_ws), L.stream_ptr())
+    return num, aux, mmb2
+
+
 def mm2_stream_project_narrow(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", ids32,
                               table, wtab32, flag=None, out=None, colmax=None, colmax_ws=None):
     """a1-a8 at narrow frame widths in ONE kernel (mmb_mm2_stream_project_narrow):
     x, aux, the MMB2 rows (and the column bounds).  Returns (x, aux, mmb2)."""
-    _require_f32_frames(audio, visual, "mm2_stream_project_narrow")
-    proj.enable_text_cache(table, wtab32)
-    num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
-    L.call("mmb_mm2_stream_project_narrow", L.ptr(ids32), L.ptr(table), table.shape[0],
-           L.ptr(wtab32), L.ptr(proj.text_cache), L.ptr(audio), L.ptr(visual), n, t, d, a, vd,
-           L.ptr(proj.wpieces), L.ptr(proj.c0), L.ptr(num), L.ptr(aux), L.ptr(mmb2), L.ptr(flag),
-           L.ptr(colmax), L.ptr(colmax_ws), L.stream_ptr())
-    return num, aux, mmb2
+    return _stream_project("mm2_stream_project_narrow", False, True, (), n, t, d, a, vd, audio, visual,
+                           proj, ids32, table, wtab32, flag, out, colmax, colmax_ws)
 
 
 def mm2_stream_project_narrow_ft(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", ids32,
@@ -631,14 +643,8 @@ def mm2_stream_project_narrow_ft(n, t, d, a, vd, audio, visual, proj: "MMB2Proje
     (mmb_mm2_stream_project_narrow_ft): `audio` / `visual` may both be float16
     or both bfloat16, from an 8-byte aligned base, and the outputs are bit for
     bit those of the same frames upcast to float32.  Returns (x, aux, mmb2)."""
-    kind = frame_kind(audio, visual, "mm2_stream_project_narrow_ft")
-    proj.enable_text_cache(table, wtab32)
-    num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
-    L.call("mmb_mm2_stream_project_narrow_ft", L.ptr(ids32), L.ptr(table), table.shape[0],
-           L.ptr(wtab32), L.ptr(proj.text_cache), L.ptr(audio), L.ptr(visual), FRAME_KINDS[kind][1],
-           n, t, d, a, vd, L.ptr(proj.wpieces), L.ptr(proj.c0), L.ptr(num), L.ptr(aux), L.ptr(mmb2),
-           L.ptr(flag), L.ptr(colmax), L.ptr(colmax_ws), L.stream_ptr())
-    return num, aux, mmb2
+    return _stream_project("mm2_stream_project_narrow_ft", True, True, (), n, t, d, a, vd, audio, visual,
+                           proj, ids32, table, wtab32, flag, out, colmax, colmax_ws)
 
 
 def mm2_stream_project(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", ids32=None,
@@ -647,15 +653,8 @@ def mm2_stream_project(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", id
     """a6-a8 in ONE kernel (mmb_mm2_stream_project): x, aux (and the column
     bounds) as mm2_stream, plus the MMB2 rows of mm2_project -- the sums s
     stay in LDS.  Returns (x, aux, mmb2)."""
-    _require_f32_frames(audio, visual, "mm2_stream_project")
-    proj.enable_pieces()
-    num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
-    V = table.shape[0] if table is not None else 0
-    L.call("mmb_mm2_stream_project", L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32),
-           L.ptr(text_dense), L.ptr(w_dense), L.ptr(audio), L.ptr(visual), n, t, d, a, vd,
-           L.ptr(proj.wpieces), L.ptr(proj.c0), L.ptr(num), L.ptr(aux), L.ptr(mmb2), L.ptr(flag),
-           L.ptr(colmax), L.ptr(colmax_ws), L.stream_ptr())
-    return num, aux, mmb2
+    return _stream_project("mm2_stream_project", False, False, (text_dense, w_dense), n, t, d, a, vd,
+                           audio, visual, proj, ids32, table, wtab32, flag, out, colmax, colmax_ws)
 
 
 def mm2_stream_project_ft(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", ids32, table,
@@ -665,16 +664,8 @@ def mm2_stream_project_ft(n, t, d, a, vd, audio, visual, proj: "MMB2Projection",
     both be float16 or both bfloat16, from an 8-byte aligned base, and the
     outputs are bit for bit those of the same frames upcast to float32.
     Returns (x, aux, mmb2)."""
-    kind = frame_kind(audio, visual, "mm2_stream_project_ft")
-    if ids32 is None:
-        raise L.MMBError("mm2_stream_project_ft: gathered text (ids32 + table) only")
-    proj.enable_pieces()
-    num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
-    L.call("mmb_mm2_stream_project_ft", L.ptr(ids32), L.ptr(table), table.shape[0], L.ptr(wtab32),
-           L.ptr(w_dense), L.ptr(audio), L.ptr(visual), FRAME_KINDS[kind][1], n, t, d, a, vd,
-           L.ptr(proj.wpieces), L.ptr(proj.c0), L.ptr(num), L.ptr(aux), L.ptr(mmb2), L.ptr(flag),
-           L.ptr(colmax), L.ptr(colmax_ws), L.stream_ptr())
-    return num, aux, mmb2
+    return _stream_project("mm2_stream_project_ft", True, False, (w_dense,), n, t, d, a, vd, audio, visual,
+                           proj, ids32, table, wtab32, flag, out, colmax, colmax_ws)
 
 
 def _fused_outputs(n: int, d: int, device, out, colmax_ws):

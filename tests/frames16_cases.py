@@ -1,7 +1,8 @@
 """Shared inputs and references of tests/test_gpu_frames16.py (GPU) and
 tests/test_frames16_cases.py (CPU): the MMB2 stream kernels on audio / visual
-frames kept in 16-bit storage.  Plain helper module: no test is collected
-from it.
+frames kept in 16-bit storage; and the scaffolding of the `_ft` entry points'
+argument tables (this one's, fused_frames16_cases', narrow_frames16_cases').
+Plain helper module: no test is collected from it.
 
 A case is one of mmb2_cases (D, A, Vd, T, N, V); a kind is "bf16" or "f16"
 (pipeline.FRAME_KINDS).  The case's U(-1, 1) frames are rounded to the kind on
@@ -16,12 +17,41 @@ from __future__ import annotations
 import functools
 
 import numpy as np
+import pytest
 import torch
 
 import mmb2_cases as C
+import mmb_lib
 from oracle import mmb2_oracle as M
 
 KINDS = {"bf16": torch.bfloat16, "f16": torch.float16}
+
+# ---------------------------------------------------------------- argument tables
+# An `_ft` entry point's table is ARGS (its parameter names), BASE (a call it
+# takes) and rows (what, change, want): BASE with `change` returns `want`.
+# Nothing is launched: the checks and the empty call return first.
+P = 0x7F0000001000  # a stand-in device pointer: 16-byte aligned, never dereferenced
+EINVAL, OK = -1, 0
+F32, F16, BF16 = mmb_lib.MMB_FRAMES_F32, mmb_lib.MMB_FRAMES_F16, mmb_lib.MMB_FRAMES_BF16
+ALL_TYPES = (("f32", F32), ("f16", F16), ("bf16", BF16))
+TYPES16 = ALL_TYPES[1:]
+
+
+def arg_rows(types, rows):
+    """Every (what, change, want) of `rows` once per frame type of `types`:
+    named "<type> <what>", the one thing changed beside that frame_type."""
+    return [(f"{name} {what}", dict(frame_type=ft, **change), want)
+            for name, ft in types for what, change, want in rows]
+
+
+def check_arg_row(entry, args, base, change, want):
+    """The call of `entry` on `base` with `change` returns `want`."""
+    call = [dict(base, **change)[k] for k in args]
+    if want == OK:
+        assert mmb_lib.call(entry, *call) == 0
+    else:
+        with pytest.raises(mmb_lib.MMBError, match=r"code -1 \(invalid argument\)"):
+            mmb_lib.call(entry, *call)
 
 # the steps test_gpu_frames16.py compares with the oracle: (D, A, Vd, T, N), V = DEFAULT_V
 STEP = [C.STEP[0], C.STEP[1], (300, 300, 300, 40, 97), (300, 76, 48, 20, 97), (50, 76, 48, 130, 16)]

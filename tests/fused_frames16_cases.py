@@ -13,8 +13,8 @@ MMB2 rows, the column bounds and the flag word.
 from __future__ import annotations
 
 import frames16_cases as F
-import mmb_lib
 import test_gpu_fused_tail as FT
+from frames16_cases import BF16, EINVAL, F32, OK, P
 
 KINDS = F.KINDS
 
@@ -44,24 +44,21 @@ STEP = (300, 300, 300, 40, 97)
 STEP_UNCHANGED = [(300, 76, 48, 20, 97), (50, 76, 48, 130, 16)]
 
 # ---------------------------------------------------------------- the argument table
-P = 0x7F0000001000  # a stand-in device pointer: 16-byte aligned, never dereferenced
 ARGS = ("ids table v wtab32 w_dense audio visual frame_type n t d a vd wpieces c0 num_out aux_out "
         "mmb2_out flag colmax colmax_ws stream").split()
-F32, F16, BF16 = mmb_lib.MMB_FRAMES_F32, mmb_lib.MMB_FRAMES_F16, mmb_lib.MMB_FRAMES_BF16
 BASE = dict(ids=P, table=P, v=1000, wtab32=P, w_dense=None, audio=P, visual=P, frame_type=BF16, n=100,
             t=40, d=300, a=300, vd=300, wpieces=P, c0=P, num_out=P, aux_out=P, mmb2_out=P, flag=None,
             colmax=None, colmax_ws=None, stream=None)
-EINVAL, OK = -1, 0
 ARG_CASES = [("frame_type -1", dict(frame_type=-1), EINVAL),
              ("frame_type 3", dict(frame_type=3), EINVAL)]
-for _name, _ft in (("f32", F32), ("f16", F16), ("bf16", BF16)):
-    ARG_CASES.append((f"{_name} n 0", dict(frame_type=_ft, n=0), OK))
-    ARG_CASES.append((f"{_name} audio 4 bytes off", dict(frame_type=_ft, audio=P + 4), EINVAL))
-for _name, _ft in (("f16", F16), ("bf16", BF16)):
-    ARG_CASES += [(f"{_name} null ids", dict(frame_type=_ft, ids=None), EINVAL),
-                  (f"{_name} audio 2 bytes off", dict(frame_type=_ft, audio=P + 2), EINVAL),
-                  (f"{_name} visual 4 bytes off", dict(frame_type=_ft, visual=P + 4), EINVAL),
-                  (f"{_name} D 252", dict(frame_type=_ft, d=252), EINVAL),
-                  (f"{_name} D 320", dict(frame_type=_ft, d=320), EINVAL),
-                  (f"{_name} A 322", dict(frame_type=_ft, a=322), EINVAL),
-                  (f"{_name} missing wpieces", dict(frame_type=_ft, wpieces=None), EINVAL)]
+ARG_CASES += F.arg_rows(F.ALL_TYPES, [("n 0", dict(n=0), OK),
+                                      ("audio 4 bytes off", dict(audio=P + 4), EINVAL)])
+ARG_CASES += F.arg_rows(F.TYPES16, [("null ids", dict(ids=None), EINVAL),
+                                    ("audio 2 bytes off", dict(audio=P + 2), EINVAL),
+                                    ("visual 4 bytes off", dict(visual=P + 4), EINVAL),
+                                    ("D 252", dict(d=252), EINVAL),
+                                    ("D 320", dict(d=320), EINVAL),
+                                    ("A 322", dict(a=322), EINVAL),
+                                    ("missing wpieces", dict(wpieces=None), EINVAL)])
+# an f32 column unit is 16 bytes: half a unit off is whole units for the 16-bit types only
+ARG_CASES.append(("f32 audio 8 bytes off", dict(frame_type=F32, audio=P + 8), EINVAL))

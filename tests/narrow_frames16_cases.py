@@ -12,7 +12,7 @@ planes, the MMB2 rows, the column bounds and the flag word.
 from __future__ import annotations
 
 import frames16_cases as F
-import mmb_lib
+from frames16_cases import BF16, EINVAL, F32, OK, P
 
 KINDS = F.KINDS
 D = 300
@@ -87,29 +87,27 @@ STEP = (D, 76, 48, 20, 3000, 3016)
 PLAN_UNCHANGED = {"c3": "wide frames", "pom": "T > 64", "mid": "wide frames"}
 
 # ---------------------------------------------------------------- the argument table
-P = 0x7F0000001000  # a stand-in device pointer: 16-byte aligned, never dereferenced
 ARGS = ("ids table v wtab32 text_cache audio visual frame_type n t d a vd wpieces c0 num_out aux_out "
         "mmb2_out flag colmax colmax_ws stream").split()
-F32, F16, BF16 = mmb_lib.MMB_FRAMES_F32, mmb_lib.MMB_FRAMES_F16, mmb_lib.MMB_FRAMES_BF16
 BASE = dict(ids=P, table=P, v=3016, wtab32=P, text_cache=P, audio=P, visual=P, frame_type=BF16, n=100,
             t=20, d=D, a=76, vd=48, wpieces=P, c0=P, num_out=P, aux_out=P, mmb2_out=P, flag=None,
             colmax=None, colmax_ws=None, stream=None)
-EINVAL, OK = -1, 0
 ARG_CASES = [("frame_type -1", dict(frame_type=-1), EINVAL),
              ("frame_type 3", dict(frame_type=3), EINVAL)]
-for _name, _ft in (("f32", F32), ("f16", F16), ("bf16", BF16)):
-    ARG_CASES += [(f"{_name} n 0", dict(frame_type=_ft, n=0), OK),
-                  (f"{_name} audio 4 bytes off", dict(frame_type=_ft, audio=P + 4), EINVAL),
-                  (f"{_name} visual 4 bytes off", dict(frame_type=_ft, visual=P + 4), EINVAL),
-                  (f"{_name} null ids", dict(frame_type=_ft, ids=None), EINVAL),
-                  (f"{_name} null text cache", dict(frame_type=_ft, text_cache=None), EINVAL),
-                  (f"{_name} null wpieces", dict(frame_type=_ft, wpieces=None), EINVAL),
-                  (f"{_name} A 128 Vd 100", dict(frame_type=_ft, a=128, vd=100), EINVAL),  # kq > 256
-                  (f"{_name} V 16385", dict(frame_type=_ft, v=16385), EINVAL),
-                  (f"{_name} D 256", dict(frame_type=_ft, d=256), EINVAL),
-                  (f"{_name} D 304", dict(frame_type=_ft, d=304), EINVAL)]
-for _name, _ft in (("f16", F16), ("bf16", BF16)):
-    ARG_CASES += [(f"{_name} audio 2 bytes off", dict(frame_type=_ft, audio=P + 2), EINVAL),
-                  (f"{_name} visual 2 bytes off", dict(frame_type=_ft, visual=P + 2), EINVAL),
-                  # whole 8-byte units: past the checks (the empty call returns before any launch)
-                  (f"{_name} n 0 frames 8 bytes off", dict(frame_type=_ft, n=0, audio=P + 8, visual=P + 8), OK)]
+ARG_CASES += F.arg_rows(F.ALL_TYPES, [("n 0", dict(n=0), OK),
+                                      ("audio 4 bytes off", dict(audio=P + 4), EINVAL),
+                                      ("visual 4 bytes off", dict(visual=P + 4), EINVAL),
+                                      ("null ids", dict(ids=None), EINVAL),
+                                      ("null text cache", dict(text_cache=None), EINVAL),
+                                      ("null wpieces", dict(wpieces=None), EINVAL),
+                                      ("A 128 Vd 100", dict(a=128, vd=100), EINVAL),  # kq > 256
+                                      ("V 16385", dict(v=16385), EINVAL),
+                                      ("D 256", dict(d=256), EINVAL),
+                                      ("D 304", dict(d=304), EINVAL)])
+ARG_CASES += F.arg_rows(F.TYPES16, [
+    ("audio 2 bytes off", dict(audio=P + 2), EINVAL),
+    ("visual 2 bytes off", dict(visual=P + 2), EINVAL),
+    # whole 8-byte units: past the checks (the empty call returns before any launch)
+    ("n 0 frames 8 bytes off", dict(n=0, audio=P + 8, visual=P + 8), OK)])
+# an f32 column unit is 16 bytes: half a unit off is whole units for the 16-bit types only
+ARG_CASES.append(("f32 audio 8 bytes off", dict(frame_type=F32, audio=P + 8), EINVAL))

@@ -17,28 +17,24 @@ import frames16_cases as F
 import mmb2_cases as C
 import mmb_lib
 import test_host_logic as H
+from frames16_cases import BF16, EINVAL, F16, F32, OK, P
 
-P = 0x7F0000001000  # a stand-in device pointer: 16-byte aligned, never dereferenced
 ARGS = ("ids table v wtab32 w_dense audio visual frame_type n t d a vd num_out s_out s_half aux_out "
         "flag colmax colmax_ws stream").split()
-BASE = dict(ids=P, table=P, v=1000, wtab32=P, w_dense=None, audio=P, visual=P, frame_type=mmb_lib.MMB_FRAMES_BF16,
-            n=100, t=40, d=300, a=300, vd=300, num_out=P, s_out=P, s_half=1, aux_out=P, flag=None,
+BASE = dict(ids=P, table=P, v=1000, wtab32=P, w_dense=None, audio=P, visual=P, frame_type=BF16, n=100,
+            t=40, d=300, a=300, vd=300, num_out=P, s_out=P, s_half=1, aux_out=P, flag=None,
             colmax=None, colmax_ws=None, stream=None)
-F32, F16, BF16 = mmb_lib.MMB_FRAMES_F32, mmb_lib.MMB_FRAMES_F16, mmb_lib.MMB_FRAMES_BF16
-EINVAL, OK = -1, 0
 CASES = [("frame_type -1", dict(frame_type=-1), EINVAL),
          ("frame_type 3", dict(frame_type=3), EINVAL),
          ("frame_type 3, n 0", dict(frame_type=3, n=0), EINVAL)]
-for _name, _ft in (("f32", F32), ("f16", F16), ("bf16", BF16)):
-    CASES.append((f"{_name} n 0", dict(frame_type=_ft, n=0), OK))
-    CASES.append((f"{_name} bounds without workspace", dict(frame_type=_ft, colmax=P), EINVAL))
-    CASES.append((f"{_name} scalar A 321", dict(frame_type=_ft, a=321), EINVAL))
-    CASES.append((f"{_name} scalar Vd 321", dict(frame_type=_ft, vd=321), EINVAL))
-    CASES.append((f"{_name} bounds at D 644", dict(frame_type=_ft, d=644, colmax=P, colmax_ws=P), EINVAL))
-    CASES.append((f"{_name} dense text (no ids)", dict(frame_type=_ft, ids=None), EINVAL))
-for _name, _ft in (("f16", F16), ("bf16", BF16)):
-    CASES.append((f"{_name} odd audio pointer", dict(frame_type=_ft, audio=P + 1), EINVAL))
-    CASES.append((f"{_name} odd visual pointer, n 0", dict(frame_type=_ft, visual=P + 3, n=0), EINVAL))
+CASES += F.arg_rows(F.ALL_TYPES, [("n 0", dict(n=0), OK),
+                                  ("bounds without workspace", dict(colmax=P), EINVAL),
+                                  ("scalar A 321", dict(a=321), EINVAL),
+                                  ("scalar Vd 321", dict(vd=321), EINVAL),
+                                  ("bounds at D 644", dict(d=644, colmax=P, colmax_ws=P), EINVAL),
+                                  ("dense text (no ids)", dict(ids=None), EINVAL)])
+CASES += F.arg_rows(F.TYPES16, [("odd audio pointer", dict(audio=P + 1), EINVAL),
+                                ("odd visual pointer, n 0", dict(visual=P + 3, n=0), EINVAL)])
 
 
 def test_signature_mirrors_the_header():
@@ -48,12 +44,7 @@ def test_signature_mirrors_the_header():
 
 @pytest.mark.parametrize("what,change,want", CASES, ids=[c[0].replace(" ", "_") for c in CASES])
 def test_stream_ft_argument_table_without_gpu(what, change, want):
-    args = [dict(BASE, **change)[k] for k in ARGS]
-    if want == OK:
-        assert mmb_lib.call("mmb_mm2_stream_ft", *args) == 0
-    else:
-        with pytest.raises(mmb_lib.MMBError, match=r"code -1 \(invalid argument\)"):
-            mmb_lib.call("mmb_mm2_stream_ft", *args)
+    F.check_arg_row("mmb_mm2_stream_ft", ARGS, BASE, change, want)
 
 
 # ---------------------------------------------------------------- the plan

@@ -46,12 +46,7 @@ def test_argument_table_starts_from_a_supported_call():
 
 @pytest.mark.parametrize("what,change,want", FF.ARG_CASES, ids=[c[0].replace(" ", "_") for c in FF.ARG_CASES])
 def test_stream_project_ft_argument_table_without_gpu(what, change, want):
-    args = [dict(FF.BASE, **change)[k] for k in FF.ARGS]
-    if want == FF.OK:
-        assert mmb_lib.call("mmb_mm2_stream_project_ft", *args) == 0
-    else:
-        with pytest.raises(mmb_lib.MMBError, match=r"code -1 \(invalid argument\)"):
-            mmb_lib.call("mmb_mm2_stream_project_ft", *args)
+    F.check_arg_row("mmb_mm2_stream_project_ft", FF.ARGS, FF.BASE, change, want)
 
 
 # ---------------------------------------------------------------- the plan

@@ -17,8 +17,6 @@ the suite's bars (MMB2 rows 1e-5, PC 1e-10, SIF rows 2^-23);
 tests/test_frames16_cases.py pins the family's conditions on those inputs.
 Product library only.
 """
-import copy
-
 import numpy as np
 import pytest
 import torch
@@ -27,35 +25,14 @@ import frames16_cases as F
 import mmb2_cases as C
 import mmb_lib as L
 import pipeline as P
+from frames16_gpu import (_assert_graph_replays, _bufs, _check_oracle, _colmax_bufs, _dev, _networks, _off, _run,
+                          _step_inputs, _untouched)
 from oracle import mmb2_oracle as M
-from oracle import sif_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-5            # the end-to-end bar of the suite
-F32_ROW = 2.0 ** -23  # SIF rows: f32 rounding of the row's largest element, doubled
 MODES = ("ids+table", "ids+w")
 KIND_IDS = list(F.KINDS)
-
-
-def _dev(a, gpu, dtype=None):
-    t = a if isinstance(a, torch.Tensor) else torch.tensor(np.asarray(a))
-    return (t if dtype is None else t.to(dtype)).to(gpu)
-
-
-def _off(t, elements):
-    """A contiguous copy of `t` that starts `elements` elements past a 16-byte boundary."""
-    flat = torch.empty(t.numel() + elements, dtype=t.dtype, device=t.device)
-    out = flat[elements:].view(t.shape)
-    out.copy_(t)
-    assert out.is_contiguous() and out.data_ptr() % 16 == elements * t.element_size()
-    return out
-
-
-def _colmax_bufs(D, gpu):
-    nb = L.query("mmb_mm2_colmax_ws_bytes", D)
-    return (torch.zeros(D, dtype=torch.int32, device=gpu),
-            torch.empty((nb + 15) // 16 * 16, dtype=torch.uint8, device=gpu))
 
 
 def _is_narrow_route(case, mode, s_half):
@@ -192,11 +169,6 @@ def _sentinel_out(N, D, kp, s_half, gpu):
     return num, s, aux
 
 
-def _untouched(out):
-    torch.cuda.synchronize()
-    return all(bool((t == -7.0).all()) for t in out)
-
-
 def test_mirror_rejections_leave_the_outputs_untouched(gpu):
     case = C.case_of((52, 8, 12, 70), 4)
     D, A, Vd, T, N, V = case
@@ -233,12 +205,10 @@ def test_fused_fronts_reject_16_bit_frames(gpu):
     D, A, Vd, T, N, V = case
     assert P.stream_project_supported(T, D, A, Vd) and P.narrow_fused_supported(T, D, A, Vd, V)
     z = C.inputs(case)
-    nets = copy.deepcopy(C.generator(D, A, Vd)).to(gpu).networks()
-    proj = P.MMB2Projection(nets, D, A, Vd, T, gpu)
+    proj = P.MMB2Projection(_networks(case, gpu), D, A, Vd, T, gpu)
     ids, table, wtab = _dev(z["ids"], gpu, torch.int32), _dev(z["E"], gpu), _dev(z["wt32"], gpu)
     au, vi = _dev(z["audio"], gpu).bfloat16(), _dev(z["visual"], gpu).bfloat16()
-    out = (torch.full((N, D), -7.0, device=gpu), torch.full((3, N), -7.0, device=gpu),
-           torch.full((N, D), -7.0, device=gpu))
+    out = _bufs(N, D, gpu, bounds=False, fill=-7.0)[0]
     with pytest.raises(L.MMBError, match="mm2_stream_project reads float32 frames only"):
         P.mm2_stream_project(N, T, D, A, Vd, au, vi, proj, ids32=ids, table=table, wtab32=wtab, out=out)
     with pytest.raises(L.MMBError, match="mm2_stream_project_narrow reads float32 frames only"):
@@ -247,36 +217,7 @@ def test_fused_fronts_reject_16_bit_frames(gpu):
 
 
 # ------------------------------------------------------------------ C: the step
-def _networks(case, gpu):
-    return copy.deepcopy(C.generator(*case[:3])).to(gpu).networks()
-
-
-def _step_inputs(case, kind, gpu):
-    """(the inputs with 16-bit frames, the same with their f32 upcast)."""
-    z = C.inputs(case)
-    a16, v16 = F.frames(case, kind)
-    base = {"table": _dev(z["E"], gpu), "wtab": _dev(z["wt32"], gpu), "ids": _dev(z["ids"], gpu, torch.int32)}
-    au, vi = _dev(a16, gpu), _dev(v16, gpu)
-    return dict(base, audio=au, visual=vi), dict(base, audio=au.float(), visual=vi.float())
-
-
 TWIN = dict(stream_project=False, narrow_fused=False, split_stream=False)
-
-
-def _run(step):
-    sif, mm2 = step.run(check=True)
-    torch.cuda.synchronize()
-    return sif, mm2
-
-
-def _check_oracle(case, kind, step, sif, mm2):
-    x = step.x.double().cpu().numpy()
-    eo = M.row_rel_err(mm2.cpu().numpy(), F.oracle_rows(case, kind)) / TOL
-    ep = np.abs(step.pc.cpu().numpy() - O.compute_pc(x, 1)).max() / 1e-10
-    ref = O.remove_pc(x, 1)
-    es = (np.abs(sif.cpu().numpy() - ref) / np.abs(ref).max(axis=1, keepdims=True)).max() / F32_ROW
-    print(f"{C.shape_id(case)} {kind}: MMB2 {eo:.3f} of 1e-5, PC {ep:.3f} of 1e-10, SIF rows {es:.3f} of 2^-23")
-    assert eo < 1.0 and ep < 1.0 and es <= 1.0
 
 
 @pytest.mark.parametrize("kind", KIND_IDS)
@@ -311,12 +252,7 @@ def test_fused_step_on_16_bit_frames(gpu, dims, kind):
 def test_step_graph_replays_the_bf16_step(gpu):
     case = F.step_case(F.STEP[0])
     inp16, _ = _step_inputs(case, "bf16", gpu)
-    step = P.FusedStep(inp16, _networks(case, gpu))
-    sif, mm2 = [t.clone() for t in step.run(check=True)]
-    g = P.StepGraph(step)
-    for _ in range(2):
-        s1, m1 = g.run(check=True)
-    assert torch.equal(s1, sif) and torch.equal(m1, mm2)
+    _assert_graph_replays(P.FusedStep(inp16, _networks(case, gpu)))
 
 
 @pytest.mark.parametrize("kind", KIND_IDS)

@@ -23,77 +23,38 @@ import pytest
 import torch
 
 import frames16_cases as F
+import frames16_gpu as G16
 import fused_frames16_cases as FF
 import mmb2_cases as C
 import mmb_lib as L
-import models
 import pipeline as P
-import synth
-import test_gpu_frames16 as G16
+from frames16_gpu import _assert_bit_for_bit, _bufs, _i32, _launch
 
 pytestmark = pytest.mark.gpu
 
 KIND_IDS = list(FF.KINDS)
 
 
-def _bufs(N, D, gpu, fill=None):
-    """(out, flag, colmax, colmax_ws) of one fused launch."""
-    mk = (lambda *s: torch.empty(s, device=gpu)) if fill is None else (lambda *s: torch.full(s, fill, device=gpu))
-    colmax, ws = G16._colmax_bufs(D, gpu)
-    return (mk(N, D), mk(3, N), mk(N, D)), torch.zeros(1, dtype=torch.int32, device=gpu), colmax, ws
-
-
-def _launch(front, dims, audio, visual, proj, text, gpu, **kw):
-    """(x, aux, mmb2, colmax, flag word) of the fused kernel through `front`."""
-    D, A, Vd, T, N = dims
-    out, flag, colmax, ws = _bufs(N, D, gpu)
-    x, aux, m = front(N, T, D, A, Vd, audio, visual, proj, ids32=text["ids"], table=text["table"],
-                      wtab32=text["wtab"], flag=flag, out=out, colmax=colmax, colmax_ws=ws, **kw)
-    torch.cuda.synchronize()
-    return x, aux, m, colmax, int(flag.item())
-
-
-def _i32(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _assert_bit_for_bit(got, twin, what):
-    for name, g, t in zip(("x", "aux", "mmb2", "colmax"), got, twin):
-        assert g.dtype == t.dtype and g.shape == t.shape, (what, name)
-        # on the values (a NaN would fail here: none in these inputs) and on the
-        # bits, so that +0 / -0 count as different
-        assert torch.equal(g, t), (what, name)
-        assert torch.equal(_i32(g), _i32(t)), (what, name, "bits")
-    assert got[4] == twin[4], (what, "flag", got[4], twin[4])
-
-
 def _pair(dims, a16, v16, proj, text, gpu, what):
     """The launch on the 16-bit frames and its f32 twin on their upcast."""
-    got = _launch(P.mm2_stream_project_ft, dims, a16, v16, proj, text, gpu)
-    twin = _launch(P.mm2_stream_project, dims, a16.float(), v16.float(), proj, text, gpu)
-    _assert_bit_for_bit(got, twin, what)
+    got = G16._pair((P.mm2_stream_project_ft, P.mm2_stream_project), dims, a16, v16, proj, text, gpu, what)
     assert bool(torch.isfinite(got[2]).all()) and bool((got[2].abs().amax(dim=1) > 0).all())
     return got
 
 
 def _synth_case(D, A, Vd, T, N, kind, gpu, bad=False):
-    """A device workload with frames rounded to the kind (torch's round to
-    nearest even: the caller's rounding), and the projection of a generator."""
-    inp = synth.device_workload(N, T, FF.KERNEL_V, D=D, A=A, Vd=Vd, seed=83, device=gpu,
-                                frame_dtype=FF.KINDS[kind])
-    assert inp["audio"].dtype == inp["visual"].dtype == FF.KINDS[kind]
+    """G16._synth_case over KERNEL_V words, with out-of-range ids if `bad`."""
+    inp, proj = G16._synth_case(D, A, Vd, T, N, FF.KERNEL_V, kind, gpu)
     if bad:  # a negative id wraps (weight 0); an id >= V is flagged and contributes a zero row
         inp["ids"][3, 5] = -7
         inp["ids"][N // 2, T - 1] = FF.KERNEL_V + 11
-    torch.manual_seed(0)
-    gen = models.AudioVisualGeneratorMultimodal(D, A, Vd, norm=None).to(gpu)
-    return inp, P.MMB2Projection(gen.networks(), D, A, Vd, T, gpu)
+    return inp, proj
 
 
 # ------------------------------------------------------------------ A: the kernel, bit for bit
 @pytest.mark.parametrize("kind", KIND_IDS)
-@pytest.mark.parametrize("D,A,Vd,T,N,bad", FF.KERNEL_CASES, ids=[G16.C.shape_id(c[:5]) + ("-bad" if c[5] else "")
-                                                                  for c in FF.KERNEL_CASES])
+@pytest.mark.parametrize("D,A,Vd,T,N,bad", FF.KERNEL_CASES, ids=[C.shape_id(c[:5]) + ("-bad" if c[5] else "")
+                                                              for c in FF.KERNEL_CASES])
 def test_fused_kernel_bit_for_bit(gpu, D, A, Vd, T, N, bad, kind):
     assert P.stream_project_supported(T, D, A, Vd)
     inp, proj = _synth_case(D, A, Vd, T, N, kind, gpu, bad)
@@ -229,8 +190,4 @@ def test_step_graph_replays_the_bf16_fused_step(gpu):
     inp16, _ = G16._step_inputs(case, "bf16", gpu)
     step = P.FusedStep(inp16, G16._networks(case, gpu), fused_frames16=True)
     assert step.plan.front == "fused"
-    sif, mm2 = [t.clone() for t in step.run(check=True)]
-    g = P.StepGraph(step)
-    for _ in range(2):
-        s1, m1 = g.run(check=True)
-    assert torch.equal(s1, sif) and torch.equal(m1, mm2)
+    G16._assert_graph_replays(step)

@@ -30,13 +30,14 @@ import pytest
 import torch
 
 import frames16_cases as F
+import frames16_gpu as G16
 import mmb2_cases as C
 import mmb_lib as L
 import models
 import narrow_frames16_cases as NF
 import pipeline as P
 import synth
-import test_gpu_frames16 as G16
+from frames16_gpu import _assert_bit_for_bit, _bufs, _i32, _launch
 from oracle import mmb2_oracle as M
 from oracle import sif_oracle as O
 
@@ -59,58 +60,13 @@ def _guarded(t16, extra=0):
     return view
 
 
-def _bufs(N, D, gpu, bounds=True, fill=None):
-    """(out, flag, colmax, colmax_ws) of one launch."""
-    mk = (lambda *s: torch.empty(s, device=gpu)) if fill is None else (lambda *s: torch.full(s, fill, device=gpu))
-    colmax, ws = G16._colmax_bufs(D, gpu) if bounds else (None, None)
-    return (mk(N, D), mk(3, N), mk(N, D)), torch.zeros(1, dtype=torch.int32, device=gpu), colmax, ws
-
-
-def _launch(front, dims, audio, visual, proj, text, gpu, bounds=True):
-    """(x, aux, mmb2, colmax or None, flag word) of the narrow fused kernel through `front`."""
-    D, A, Vd, T, N = dims
-    out, flag, colmax, ws = _bufs(N, D, gpu, bounds)
-    x, aux, m = front(N, T, D, A, Vd, audio, visual, proj, ids32=text["ids"], table=text["table"],
-                      wtab32=text["wtab"], flag=flag, out=out, colmax=colmax, colmax_ws=ws)
-    torch.cuda.synchronize()
-    return x, aux, m, colmax, int(flag.item())
-
-
-def _i32(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _assert_bit_for_bit(got, twin, what, nan_rows=False):
-    for name, g, t in zip(("x", "aux", "mmb2", "colmax"), got, twin):
-        if t is None:
-            assert g is None, (what, name)
-            continue
-        assert g.dtype == t.dtype and g.shape == t.shape, (what, name)
-        # on the bits, so that +0 / -0 count as different ...
-        assert torch.equal(_i32(g), _i32(t)), (what, name, "bits")
-        # ... and on the values; a zero-weight utterance's x row is 0 / 0 (nan_rows):
-        # there the values are compared beside the NaNs, which the bits cover
-        if nan_rows and g.is_floating_point():
-            assert torch.equal(torch.isnan(g), torch.isnan(t)), (what, name, "NaN places")
-            g, t = g[~torch.isnan(g)], t[~torch.isnan(t)]
-        assert torch.equal(g, t), (what, name)
-    assert got[4] == twin[4], (what, "flag", got[4], twin[4])
-
-
-def _pair(dims, a16, v16, proj, text, gpu, what, bounds=True, nan_rows=False):
-    """The launch on the 16-bit frames and its f32 twin on their upcast."""
-    got = _launch(P.mm2_stream_project_narrow_ft, dims, a16, v16, proj, text, gpu, bounds)
-    twin = _launch(P.mm2_stream_project_narrow, dims, a16.float(), v16.float(), proj, text, gpu, bounds)
-    _assert_bit_for_bit(got, twin, what, nan_rows)
-    return got
+# the launch on the 16-bit frames and its f32 twin on their upcast
+_pair = functools.partial(G16._pair, (P.mm2_stream_project_narrow_ft, P.mm2_stream_project_narrow))
 
 
 def _synth_case(A, Vd, T, N, V, kind, gpu, bad=False):
-    """A device workload with frames rounded to the kind (torch's round to
-    nearest even: the caller's rounding) inside guarded allocations, and the
-    projection of a generator."""
-    inp = synth.device_workload(N, T, V, D=NF.D, A=A, Vd=Vd, seed=83, device=gpu, frame_dtype=NF.KINDS[kind])
-    assert inp["audio"].dtype == inp["visual"].dtype == NF.KINDS[kind]
+    """G16._synth_case with the frames inside guarded allocations."""
+    inp, proj = G16._synth_case(NF.D, A, Vd, T, N, V, kind, gpu)
     inp["audio"], inp["visual"] = _guarded(inp["audio"]), _guarded(inp["visual"])
     zero_row = None
     if bad:
@@ -123,9 +79,7 @@ def _synth_case(A, Vd, T, N, V, kind, gpu, bad=False):
         inp["ids"][3, min(5, T - 1)] = -7
         inp["ids"][N - 1, 0] = -3
         inp["ids"][N // 2, T - 1] = V + 11
-    torch.manual_seed(0)
-    gen = models.AudioVisualGeneratorMultimodal(NF.D, A, Vd, norm=None).to(gpu)
-    return inp, P.MMB2Projection(gen.networks(), NF.D, A, Vd, T, gpu), zero_row
+    return inp, proj, zero_row
 
 
 # ------------------------------------------------------------------ A: the kernel, bit for bit
@@ -295,11 +249,7 @@ def test_step_graph_replays_the_bf16_narrow_fused_step(gpu):
     inp16, _ = _step_inputs("bf16", gpu)
     step = P.FusedStep(inp16, _generator(gpu).networks(), narrow_frames16=True)
     assert step.plan.front == "narrow_fused"
-    sif, mm2 = [t.clone() for t in step.run(check=True)]
-    g = P.StepGraph(step)
-    for _ in range(2):
-        s1, m1 = g.run(check=True)
-    assert torch.equal(s1, sif) and torch.equal(m1, mm2)
+    G16._assert_graph_replays(step)
 
 
 @pytest.mark.parametrize("kind", KIND_IDS)

@@ -73,12 +73,7 @@ def test_argument_table_starts_from_a_supported_call():
 
 @pytest.mark.parametrize("what,change,want", NF.ARG_CASES, ids=[c[0].replace(" ", "_") for c in NF.ARG_CASES])
 def test_stream_project_narrow_ft_argument_table_without_gpu(what, change, want):
-    args = [dict(NF.BASE, **change)[k] for k in NF.ARGS]
-    if want == NF.OK:
-        assert mmb_lib.call(NAME, *args) == 0
-    else:
-        with pytest.raises(mmb_lib.MMBError, match=r"code -1 \(invalid argument\)"):
-            mmb_lib.call(NAME, *args)
+    F.check_arg_row(NAME, NF.ARGS, NF.BASE, change, want)
 
 
 # ---------------------------------------------------------------- the plan
