@@ -20,6 +20,21 @@
  *     kernels that meet out-of-range ids (the shim raises IndexError, like
  *     numpy would in the reference) or all-zero-weight utterances (the shim
  *     raises ValueError where the reference's PC step would).
+ *
+ * Scratch and outputs on entry: what a caller-owned workspace (`ws`,
+ * `colmax_ws`, `dh_ws`), an output buffer or a derived image (wm, c0, wsplit,
+ * wpieces, the text cache, the normalised word table) holds when a call
+ * starts is unspecified, and no output depends on it: every slot a kernel
+ * reads was written by this call (or by the builder of the image, which
+ * writes every byte its *_bytes query counts, pads included; the one gap is
+ * described at mmb_mm2_text_cache), and a pad documented as zero is written
+ * as zero.  The exceptions are stated at their
+ * entry points and are all words that workgroups synchronise on, which must
+ * be zero on entry and are left zero: the first 16 bytes of mmb_pc_solve_mc's
+ * ws and the whole ws of mmb_mlp_train (mmb_mm2_stream_project zeroes its
+ * counter at the end of colmax_ws itself).  An output that `accumulate` adds
+ * to is an input.  tests/test_gpu_scratch.py holds every entry point to this
+ * with three byte patterns.
  */
 #ifndef MMB_H_
 #define MMB_H_
@@ -463,7 +478,11 @@ int mmb_mm2_project_x3_rmpc(const void* s_split, const float* num, const float* 
  *   mmb_mm2_text_cache: cache of mmb_mm2_text_cache_bytes(v, d) bytes (16-B
  *   aligned) from the word table, the f32 weight table and the merged Wm
  *   (mmb_mm2_prepare); rebuild it when any of them changes (the launch reads
- *   the token weights from the cache's copy of wtab32).  v <= 16384.
+ *   the token weights from the cache's copy of wtab32).  v <= 16384.  The
+ *   build writes every byte of the cache except, for a table of v < 32 words,
+ *   the hot-word id slots v .. 31 (bytes [4 * 610 v, 4 * (609 v + 32)) of
+ *   the cache: rows of 608 floats, v hot-slot words, then the 32 ids): the
+ *   fused kernel reads min(v, 32) of them.
  *   wpieces: the piece-ordered weight split (mmb_mm2_split_pieces).
  * replaces: sif2.calc_weights + estimate_embedding_overall_gpu2
  *   /root/reference/sif2.py:103-114,164-208 with the text gather of
@@ -551,7 +570,8 @@ int mmb_mlp_eval(const float* latents, const float* labels, const int64_t* perm,
  * v_perm[k * n_valid ...] (k = the k-th such epoch of this launch) with the
  * weights of that moment go to valid_loss[k * ceil(n_valid / batch) + j].
  * ws: scratch of mmb_mlp_workspace_bytes(d, h) bytes (16-B aligned), ZEROED
- * by the caller before its first use (a completed launch leaves it zeroed);
+ * by the caller before its first use (a completed launch leaves ALL of it
+ * zero, the exchange slots it used as well as the control words);
  * flag (nullable) gets MMB_FLAG_SYNC_TIMEOUT if the workgroups' exchange
  * stalls (~1 s) or finds ws dirty (the parameters are then invalid and ws
  * must be re-zeroed).  The P = ceil(h / 32) workgroups are launched

@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kTrNT) void mlp_train_mc_kernel(TrainArgs a) {
   float* sb2 = sb1 + 32;                                // [O]
   float* s_red = sb2 + O;                               // [8]
   float* sdh = spart;                                   // [32][32]
-  __shared__ int s_abort;
+  __shared__ int s_abort, s_last;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -378,12 +378,18 @@ __global__ __launch_bounds__(kTrNT) void mlp_train_mc_kernel(TrainArgs a) {
   }
 
   // the last workgroup past its final exchange returns the counter to 0 (the
-  // next launch then needs no memset to find it there)
+  // next launch then needs no memset to find it there) and, every workgroup
+  // being past its last read of the shares, zeroes the exchange slots of this
+  // launch: a completed launch leaves the WHOLE workspace as it was handed
+  // over (include/mmb.h), not only its control words
   if (tid == 0) {
     const unsigned old = __hip_atomic_fetch_add(a.ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == static_cast<unsigned>(a.P) * (xc + 1) - 1)
-      __hip_atomic_store(a.ctl, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = old == static_cast<unsigned>(a.P) * (xc + 1) - 1;
+    if (s_last) __hip_atomic_store(a.ctl, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+  __syncthreads();
+  if (s_last)
+    for (int e = tid; e < 2 * a.P * kBatchMax * O; e += kTrNT) a.xbuf[e] = 0.f;
   // write this tile's parameters back (b2 by workgroup 0)
 #pragma unroll
   for (int j = 0; j < kFT; ++j) {

@@ -151,6 +151,16 @@ def test_dropins_reject_d513_and_npc7(gpu):
 
 
 # ------------------------------------------------------------------ 2: the Gram alone
+def _check_gram(G, ref, what):
+    """G (device or numpy) is symmetric and within 1e-13 of max |G| of the
+    exact f64 Gram `ref`; returns the error."""
+    G = G.cpu().numpy() if isinstance(G, torch.Tensor) else G
+    assert np.array_equal(G, G.T), what
+    e = _note(2, "Gram", np.abs(G - ref).max() / np.abs(ref).max(), 1e-13)
+    assert e < 1e-13, (what, e)
+    return e
+
+
 @pytest.mark.parametrize("n,d", W.SHAPES, ids=[W.shape_id(s) for s in W.SHAPES])
 def test_gram_routes(gpu, n, d):
     num32 = W.x32(n, d).astype(np.float32)
@@ -160,11 +170,7 @@ def test_gram_routes(gpu, n, d):
 
     def check(G, ref, what):
         nonlocal worst
-        G = G.cpu().numpy()
-        assert np.array_equal(G, G.T), what
-        e = _note(2, "Gram", np.abs(G - ref).max() / np.abs(ref).max(), 1e-13)
-        worst = max(worst, e)
-        assert e < 1e-13, (what, e)
+        worst = max(worst, _check_gram(G, ref, what))
 
     X = _x_of(num32, None)
     exact = X.T @ X
@@ -181,16 +187,17 @@ def test_gram_routes(gpu, n, d):
 
 
 # ------------------------------------------------------------------ 3: the int8 Gram
-@pytest.mark.parametrize("n", [7, 320, 5000])
-@pytest.mark.parametrize("d", [4, 12, 20, 64, 260, 304])
-def test_gram_i8_widths(gpu, n, d):
+def _i8_rows(n, d):
+    """Heavy-tailed t(3) rows with one all-zero column (f32)."""
     rng = np.random.default_rng(1000 * n + d)
     x = rng.standard_t(3, size=(n, d)).astype(np.float32)
     x[:, d // 2] = 0.0
-    xt = _dev(x, gpu)
-    cm = P.colmax(xt)
-    assert np.array_equal(cm.cpu().numpy().view(np.float32), np.abs(x).max(0))
-    G = P.gram_i8(xt, cm).cpu().numpy()
+    return x
+
+
+def _check_gram_i8(G, x):
+    """The int8 Gram G (numpy) of the f32 rows x: symmetric, 1e-13 against the
+    sliced oracle, 2e-9 against the exact f64 Gram."""
     ref = O.sliced_gram(x)
     exact = x.astype(np.float64).T @ x.astype(np.float64)
     e1 = _note(3, "vs sliced oracle", np.abs(G - ref).max() / np.abs(ref).max(), 1e-13)
@@ -198,6 +205,16 @@ def test_gram_i8_widths(gpu, n, d):
     print(f"int8 Gram vs sliced oracle {e1:.3e} (bar 1e-13), vs exact {e2:.3e} (bar 2e-9)")
     assert e1 <= 1e-13 and e2 <= 2e-9
     assert np.array_equal(G, G.T)
+
+
+@pytest.mark.parametrize("n", [7, 320, 5000])
+@pytest.mark.parametrize("d", [4, 12, 20, 64, 260, 304])
+def test_gram_i8_widths(gpu, n, d):
+    x = _i8_rows(n, d)
+    xt = _dev(x, gpu)
+    cm = P.colmax(xt)
+    assert np.array_equal(cm.cpu().numpy().view(np.float32), np.abs(x).max(0))
+    _check_gram_i8(P.gram_i8(xt, cm).cpu().numpy(), x)
 
 
 @pytest.mark.parametrize("d", [308, 302])
