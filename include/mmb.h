@@ -325,6 +325,37 @@ int mmb_mm2_stream_split(const int32_t* ids, const float* table, int64_t v, cons
                          int32_t* flag, uint32_t* colmax, void* colmax_ws, int parts, void* ws,
                          size_t ws_bytes, hipStream_t stream);
 
+/* mmb_mm2_stream_split on audio / visual frames of storage type frame_type
+ * (MMB_FRAMES_*, as mmb_mm2_stream_ft): POM's long transcripts with the frames
+ * kept in 16 bits.  Text is gathered (ids + table, weights from wtab32 or per
+ * token from w_dense); both frame tensors, [n,t,a] and [n,t,vd] contiguous,
+ * hold elements of frame_type.  Only the frame workgroups read them: a frame
+ * value is widened to f32 in registers right after its (non-temporal) load --
+ * exact for both 16-bit types, fp16 subnormals included -- and summed by the
+ * statements of the f32 kernel in their order; the partial sums in ws are f32,
+ * so the second kernel is mmb_mm2_stream_split's.  Every output -- x, s, aux,
+ * the column bounds and the flag word -- is bit for bit what
+ * mmb_mm2_stream_split writes, with the same parts, for the same frames upcast
+ * to f32 by the caller (and, with one range, what mmb_mm2_stream_ft's
+ * workgroup kernel writes).  The library rounds nothing: the caller chose the
+ * 16-bit values.  parts, ws (mmb_mm2_stream_split_ws_bytes: the same bytes for
+ * every frame type), outputs, layouts, the empty call (n == 0, before the
+ * workspace is looked at) and the flag bits are mmb_mm2_stream_split's.
+ * MMB_FRAMES_F32 is mmb_mm2_stream_split itself for the same arguments.
+ * 16-bit frames: a modality in 4-value units (one 8-byte load) when its width
+ * % 4 == 0 and its base is 8-byte aligned (up to 1280 wide), in scalar 2-byte
+ * loads if not (up to 320); 3 d + 2 a + 2 vd <= 2240 as for f32.
+ * MMB_EINVAL before any launch: a frame_type outside 0..2, null ids, a 16-bit
+ * frame base that is not 2-byte aligned, anything mmb_mm2_stream_split rejects.
+ * replaces: the frame loops of sif2.estimate_embedding_overall_gpu2
+ *   sif2.py:181-205 (which reads f32 frames only) at the per-split call sites
+ *   simplesif.py:308-311 (POM's long transcripts)                            */
+int mmb_mm2_stream_split_ft(const int32_t* ids, const float* table, int64_t v, const float* wtab32,
+                            const float* w_dense, const void* audio, const void* visual, int frame_type,
+                            int64_t n, int t, int d, int a, int vd, float* num_out, void* s_out,
+                            int s_half, float* aux_out, int32_t* flag, uint32_t* colmax,
+                            void* colmax_ws, int parts, void* ws, size_t ws_bytes, hipStream_t stream);
+
 /* mmb_mm2_stream and mmb_mm2_project_x3 in ONE kernel (the bench step's
  * MMB2 path): the same num (x), aux[0..1] and colmax outputs as mmb_mm2_stream
  * (aux[2] is the text piece's scale) and the MMB2 rows of mmb_mm2_project_x3

@@ -304,6 +304,13 @@ __global__ __launch_bounds__(NT) void utt_stream_kernel(StreamArgs a) {
 // Sxx_e (D) | count_nonzero(w), sum w, row-0 tokens, their weight sum] (row
 // 0 excluded from the sums, as utt_stream_kernel), then frame partials
 // [N][Pf][Wf] = [Sx_a (A) | Sxx_a (A) | Sx_v (Vd) | Sxx_v (Vd)].
+//
+// The frame workgroups read frames of type FE (mmb_mm2_stream_split_ft): a
+// 16-bit unit of 4 values is one 8-byte load, a scalar one a 2-byte load,
+// widened to f32 in registers (ldv_nt) and summed by the same statements in
+// the same order -- the partials, f32 in either case, are bit for bit those
+// of the upcast frames, and the text workgroups and the finish kernel do not
+// know the frame type.
 struct SplitPlan {
   int Pt, Lt, Pf, Lf;  // text / frame parts per utterance and their lengths
   int Wt, Wf;          // partial row strides (floats, multiples of 4)
@@ -315,6 +322,11 @@ struct SplitPlan {
 constexpr int kSplitTextX = 1;
 constexpr int kSplitTU = 8;
 constexpr int kSplitFU = 8;
+// the same for 16-bit frames: a frame row is half the bytes, so 16 rows keep
+// in flight what 8 f32 rows do (tools/split_ab.py --frames16, graph-timed,
+// bf16, 8 / 16 rows: valid 47.7 / 39.9 us, test 93.7 / 77.9 us; the same
+// sums bit for bit)
+constexpr int kSplitFU16 = 16;
 inline SplitPlan split_plan_of(int t, int d, int a, int vd, int Pf, int text_x = 1) {
   SplitPlan q;
   q.Lf = (t + Pf - 1) / Pf;
@@ -330,7 +342,7 @@ inline SplitPlan split_plan_of(int t, int d, int a, int vd, int Pf, int text_x =
   return q;
 }
 
-template <int VT, int VA, int VV, int FU = 16, int TU = 8>
+template <int VT, int VA, int VV, int FU = 16, int TU = 8, class FE = float>
 __global__ __launch_bounds__(kNT) void utt_split_part_kernel(StreamArgs a, SplitPlan q,
                                                              float* __restrict__ part) {
   constexpr int NT = kNT;
@@ -457,7 +469,7 @@ __global__ __launch_bounds__(kNT) void utt_split_part_kernel(StreamArgs a, Split
   const int p = static_cast<int>(bm - i * q.Pf);
   const int tb = p * q.Lf, te = min(a.L, tb + q.Lf);
   float* prow = part + ntext * q.Wt + (i * q.Pf + p) * static_cast<int64_t>(q.Wf);
-  auto stream = [&](const float* src, int F, float* out, auto vec) {
+  auto stream = [&](const FE* src, int F, float* out, auto vec) {
     constexpr int VF = decltype(vec)::value;
     const int CF = F / VF, RF = NT / CF;
     const int rF = tid / CF, cF = tid - rF * CF;
@@ -465,11 +477,11 @@ __global__ __launch_bounds__(kNT) void utt_split_part_kernel(StreamArgs a, Split
 #pragma unroll
     for (int e = 0; e < VF; ++e) sm[e] = sq[e] = 0.f;
     if (rF < RF) {
-      const float* base = src + (i * a.L) * F + cF * VF;
+      const FE* base = src + (i * a.L) * F + cF * VF;
 #pragma unroll FU
       for (int t = tb + rF; t < te; t += RF) {
         float v[VF];
-        ldv_nt<VF>(base + static_cast<int64_t>(t) * F, v);
+        ldv_nt<VF, FE>(base + static_cast<int64_t>(t) * F, v);
 #pragma unroll
         for (int e = 0; e < VF; ++e) {
           sm[e] += v[e];
@@ -495,9 +507,9 @@ __global__ __launch_bounds__(kNT) void utt_split_part_kernel(StreamArgs a, Split
     }
   };
   if (vis)
-    stream(frames<float>(a.visual), a.Vd, prow + 2 * a.A, std::integral_constant<int, VV>{});
+    stream(frames<FE>(a.visual), a.Vd, prow + 2 * a.A, std::integral_constant<int, VV>{});
   else
-    stream(frames<float>(a.audio), a.A, prow, std::integral_constant<int, VA>{});
+    stream(frames<FE>(a.audio), a.A, prow, std::integral_constant<int, VA>{});
 }
 
 // The partials of utterance i (blockIdx.x) in part order, then the row's
@@ -1634,15 +1646,64 @@ extern "C" size_t mmb_mm2_stream_split_ws_bytes(int64_t n, int t, int d, int a_,
   return split_ws_floats(n, split_plan_of(t, d, a_, vd, P, parts > 0 ? 1 : kSplitTextX)) * sizeof(float);
 }
 
-template <int VT, int VA, int VV>
+template <int VT, int VA, int VV, class FE = float>
 static int launch_split(const StreamArgs& a, const SplitPlan& q, float* part, hipStream_t stream) {
   const int64_t grid = a.N * (q.Pt + 2 * q.Pf);
-  utt_split_part_kernel<VT, VA, VV, kSplitFU, kSplitTU><<<static_cast<unsigned>(grid), kNT, 0, stream>>>(a, q, part);
+  if constexpr (std::is_same_v<FE, float>) {
+    utt_split_part_kernel<VT, VA, VV, kSplitFU, kSplitTU><<<static_cast<unsigned>(grid), kNT, 0, stream>>>(a, q, part);
+  } else {
+    // 16-bit frames (mmb_mm2_stream_split_ft): the frame branch alone reads
+    // FE; the partials are f32, so the finish kernel below is the same one
+#ifndef MMB_HOOK_SPLIT16_LAUNCH  // (tools/diag: the 16-bit frame unroll, MMB_SPLIT16_UNR)
+#define MMB_HOOK_SPLIT16_LAUNCH false
+#endif
+    if (!(MMB_HOOK_SPLIT16_LAUNCH)) {
+      utt_split_part_kernel<VT, VA, VV, kSplitFU16, kSplitTU, FE>
+          <<<static_cast<unsigned>(grid), kNT, 0, stream>>>(a, q, part);
+    }
+  }
   MMB_LAUNCH_CHECK();
   const size_t lds = a.s_half ? static_cast<size_t>(2 * (a.D + a.A + a.Vd)) * sizeof(float) : 0;
   utt_split_finish_kernel<<<static_cast<unsigned>(a.N), kNT, lds, stream>>>(a, q, part);
   MMB_LAUNCH_CHECK();
   return MMB_OK;
+}
+
+// mmb_mm2_stream_split and mmb_mm2_stream_split_ft on frames of storage type
+// frame_type (validated by the caller): the checks, the plan, the launch of
+// the kernel instantiated for the frame type, the column bounds.
+static int split_stream(int frame_type, const int32_t* ids, const float* table, int64_t v, const float* wtab32,
+                        const float* text_dense, const float* emb_dense, const float* w_dense, const void* audio,
+                        const void* visual, int64_t n, int t, int d, int a_, int vd, float* num_out, void* s_out,
+                        int s_half, float* aux_out, int32_t* flag, uint32_t* colmax, void* colmax_ws, int parts,
+                        void* ws, size_t ws_bytes, hipStream_t stream) {
+  const int fb = frame_bytes(frame_type);
+  StreamArgs s;
+  if (const int rc = stream_args(&s, ids, table, v, wtab32, text_dense, emb_dense, w_dense, audio, visual, n,
+                                 t, d, a_, vd, num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws))
+    return rc;
+  // the bounds: a partial row per utterance
+  MMB_REQUIRE(s_out && parts >= 0 && (colmax == nullptr || (d <= 2 * kNT && n <= kCmaxRows)));
+  // a 16-bit value is never read from an odd address, scalar rows included
+  MMB_REQUIRE(fb == 4 || ((reinterpret_cast<uintptr_t>(audio) | reinterpret_cast<uintptr_t>(visual)) & 1) == 0);
+  // the empty call returns before the workspace is looked at, and before
+  // mmb_mm2_stream_split_parts queries the device
+  if (n == 0) return empty_call(colmax, d, stream);
+  const int P = parts > 0 ? std::min(parts, t) : mmb_mm2_stream_split_parts(n, t);
+  const SplitPlan q = split_plan_of(t, d, a_, vd, P, parts > 0 ? 1 : kSplitTextX);
+  MMB_REQUIRE(ws && ws_bytes >= split_ws_floats(n, q) * sizeof(float));
+  MMB_REQUIRE(n * (q.Pt + 2 * q.Pf) <= (int64_t{1} << 31) - 1);
+  MMB_REQUIRE(3 * d + 2 * a_ + 2 * vd <= kSplitJ * kNT);  // the finish kernel's columns
+  const StreamVec vec = stream_vec(s, fb);
+  MMB_REQUIRE(units_fit(s, vec));
+  const int rc = dispatch3(vec.t, vec.a, vec.v, [&](auto vt, auto va, auto vv) {
+    constexpr int VT = vt.value ? 4 : 1, VA = va.value ? 4 : 1, VV = vv.value ? 4 : 1;
+    float* part = static_cast<float*>(ws);
+    return frame_type == MMB_FRAMES_F32   ? launch_split<VT, VA, VV>(s, q, part, stream)
+           : frame_type == MMB_FRAMES_F16 ? launch_split<VT, VA, VV, f16_t>(s, q, part, stream)
+                                          : launch_split<VT, VA, VV, bf16_t>(s, q, part, stream);
+  });
+  return reduce_colmax(rc, s, static_cast<int>(n), colmax, stream);
 }
 
 extern "C" int mmb_mm2_stream_split(const int32_t* ids, const float* table, int64_t v,
@@ -1652,27 +1713,21 @@ extern "C" int mmb_mm2_stream_split(const int32_t* ids, const float* table, int6
                                     float* num_out, void* s_out, int s_half, float* aux_out,
                                     int32_t* flag, uint32_t* colmax, void* colmax_ws, int parts,
                                     void* ws, size_t ws_bytes, hipStream_t stream) {
-  StreamArgs s;
-  if (const int rc = stream_args(&s, ids, table, v, wtab32, text_dense, emb_dense, w_dense, audio, visual, n,
-                                 t, d, a_, vd, num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws))
-    return rc;
-  // the bounds: a partial row per utterance
-  MMB_REQUIRE(s_out && parts >= 0 && (colmax == nullptr || (d <= 2 * kNT && n <= kCmaxRows)));
-  // the empty call returns before the workspace is looked at, and before
-  // mmb_mm2_stream_split_parts queries the device
-  if (n == 0) return empty_call(colmax, d, stream);
-  const int P = parts > 0 ? std::min(parts, t) : mmb_mm2_stream_split_parts(n, t);
-  const SplitPlan q = split_plan_of(t, d, a_, vd, P, parts > 0 ? 1 : kSplitTextX);
-  MMB_REQUIRE(ws && ws_bytes >= split_ws_floats(n, q) * sizeof(float));
-  MMB_REQUIRE(n * (q.Pt + 2 * q.Pf) <= (int64_t{1} << 31) - 1);
-  MMB_REQUIRE(3 * d + 2 * a_ + 2 * vd <= kSplitJ * kNT);  // the finish kernel's columns
-  const StreamVec vec = stream_vec(s);
-  MMB_REQUIRE(units_fit(s, vec));
-  const int rc = dispatch3(vec.t, vec.a, vec.v, [&](auto vt, auto va, auto vv) {
-    return launch_split<vt.value ? 4 : 1, va.value ? 4 : 1, vv.value ? 4 : 1>(s, q, static_cast<float*>(ws),
-                                                                             stream);
-  });
-  return reduce_colmax(rc, s, static_cast<int>(n), colmax, stream);
+  return split_stream(MMB_FRAMES_F32, ids, table, v, wtab32, text_dense, emb_dense, w_dense, audio, visual, n, t, d,
+                      a_, vd, num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws, parts, ws, ws_bytes,
+                      stream);
+}
+
+extern "C" int mmb_mm2_stream_split_ft(const int32_t* ids, const float* table, int64_t v, const float* wtab32,
+                                       const float* w_dense, const void* audio, const void* visual,
+                                       int frame_type, int64_t n, int t, int d, int a_, int vd, float* num_out,
+                                       void* s_out, int s_half, float* aux_out, int32_t* flag, uint32_t* colmax,
+                                       void* colmax_ws, int parts, void* ws, size_t ws_bytes,
+                                       hipStream_t stream) {
+  MMB_REQUIRE(frame_bytes(frame_type) != 0);
+  MMB_REQUIRE(ids);  // gathered text only
+  return split_stream(frame_type, ids, table, v, wtab32, nullptr, nullptr, w_dense, audio, visual, n, t, d, a_, vd,
+                      num_out, s_out, s_half, aux_out, flag, colmax, colmax_ws, parts, ws, ws_bytes, stream);
 }
 
 // the tools build's variant launches, knobs and probes (tools/diag/); the

@@ -27,8 +27,8 @@ MMB_FLAG_ID_RANGE = 1
 MMB_FLAG_ZERO_WEIGHTS = 2
 MMB_FLAG_SYNC_TIMEOUT = 4
 
-# frame element types of mmb_mm2_stream_ft, mmb_mm2_stream_project_ft and
-# mmb_mm2_stream_project_narrow_ft
+# frame element types of mmb_mm2_stream_ft, mmb_mm2_stream_split_ft,
+# mmb_mm2_stream_project_ft and mmb_mm2_stream_project_narrow_ft
 MMB_FRAMES_F32, MMB_FRAMES_F16, MMB_FRAMES_BF16 = 0, 1, 2
 
 _P = ctypes.c_void_p
@@ -76,6 +76,8 @@ SIGNATURES = {
     "mmb_mm2_stream_split_ws_bytes": (_S, [_L, _I, _I, _I, _I, _I]),
     "mmb_mm2_stream_split": (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P,
                                   _I, _P, _P, _P, _P, _I, _P, _S, _P]),
+    "mmb_mm2_stream_split_ft": (_I, [_P, _P, _L, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _P, _I,
+                                     _P, _P, _P, _P, _I, _P, _S, _P]),
     "mmb_mm2_stream_project_supported": (_I, [_I, _I, _I, _I]),
     "mmb_mm2_stream_project": (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P,
                                     _P, _P, _P, _P, _P, _P, _P]),

@@ -511,6 +511,33 @@ def frame_kind(audio: torch.Tensor, visual: torch.Tensor, who: str = "mm2_stream
     raise L.MMBError(f"{who}: frames must be float32, float16 or bfloat16, not {audio.dtype}")
 
 
+def _stream_outputs(who: str, kind: str, n, d, a, vd, audio, visual, text_src, out, s_half: bool, colmax_ws):
+    """(x, s, aux) of mm2_stream and mm2_stream_split_ft -- `out` if given,
+    else allocated -- after the checks both make before the call: the widths
+    against the stream kernels' limits, the s buffer's dtype, the column-bound
+    workspace's size."""
+    # a vector row: whole 4-element units from a base aligned to one unit
+    # (16 bytes of f32; 8 bytes of a 16-bit frame type)
+    unit = 16 if kind == "f32" else 8
+    for what, w, src, al in (("text", d, text_src, 16), ("audio", a, audio, unit),
+                             ("visual", vd, visual, unit)):
+        vec = w % 4 == 0 and src is not None and src.data_ptr() % al == 0
+        if w > (STREAM_MAX_VECTOR_WIDTH if vec else STREAM_MAX_SCALAR_WIDTH):
+            raise L.MMBError(f"{who}: {what} width {w} is past the stream kernels' limit: "
+                             f"{STREAM_MAX_VECTOR_WIDTH} for rows of whole float4 units (width % 4 "
+                             f"== 0, 16-byte aligned; 8-byte for 16-bit frames), "
+                             f"{STREAM_MAX_SCALAR_WIDTH} otherwise")
+    if out is None:
+        dev = audio.device
+        out = (torch.empty((n, d), dtype=torch.float32, device=dev),
+               s_buffer(n, mm2_dims(d, a, vd)[0], s_half, dev),
+               torch.empty((3, n), dtype=torch.float32, device=dev))
+    if out[1].dtype != (torch.float16 if s_half else torch.float32):
+        raise L.MMBError("s buffer dtype does not match s_half")
+    _check_colmax_ws(colmax_ws, d)
+    return out
+
+
 def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=None,
                text_dense=None, emb_dense=None, w_dense=None, flag=None, out=None,
                s_half: bool = True, colmax=None, colmax_ws=None, split=None, parts: int = 0):
@@ -527,35 +554,17 @@ def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=Non
 
     `audio` / `visual` may both be float16 or both bfloat16 instead of float32
     (mmb_mm2_stream_ft; gathered text, no `split`): the outputs are bit for bit
-    those of the same frames upcast to float32."""
-    kp, _ = mm2_dims(d, a, vd)
-    dev = audio.device
+    those of the same frames upcast to float32 (with `split`:
+    mm2_stream_split_ft)."""
     kind = frame_kind(audio, visual)
     if kind != "f32" and ids32 is None:
         raise L.MMBError(f"mm2_stream: {kind} frames go with gathered text (ids32 + table) only")
     if kind != "f32" and split is not None:
         raise L.MMBError(f"mm2_stream: the split stream reads float32 frames only, not {kind}")
     text_src = table if ids32 is not None else text_dense
-    # a vector row: whole 4-element units from a base aligned to one unit
-    # (16 bytes of f32; 8 bytes of a 16-bit frame type)
-    unit = 16 if kind == "f32" else 8
-    for what, w, src, al in (("text", d, text_src, 16), ("audio", a, audio, unit),
-                             ("visual", vd, visual, unit)):
-        vec = w % 4 == 0 and src is not None and src.data_ptr() % al == 0
-        if w > (STREAM_MAX_VECTOR_WIDTH if vec else STREAM_MAX_SCALAR_WIDTH):
-            raise L.MMBError(f"mm2_stream: {what} width {w} is past the stream kernels' limit: "
-                             f"{STREAM_MAX_VECTOR_WIDTH} for rows of whole float4 units (width % 4 "
-                             f"== 0, 16-byte aligned; 8-byte for 16-bit frames), "
-                             f"{STREAM_MAX_SCALAR_WIDTH} otherwise")
-    if out is None:
-        out = (torch.empty((n, d), dtype=torch.float32, device=dev),
-               s_buffer(n, kp, s_half, dev),
-               torch.empty((3, n), dtype=torch.float32, device=dev))
-    num, s, aux = out
-    if s.dtype != (torch.float16 if s_half else torch.float32):
-        raise L.MMBError("s buffer dtype does not match s_half")
+    num, s, aux = _stream_outputs("mm2_stream", kind, n, d, a, vd, audio, visual, text_src, out, s_half,
+                                  colmax_ws)
     V = table.shape[0] if table is not None else 0
-    _check_colmax_ws(colmax_ws, d)
     # the arguments the three entry points share: the gathered text's, the
     # frames', and everything from the shapes on
     gathered = (L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32))
@@ -571,6 +580,32 @@ def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=Non
                L.stream_ptr())
     else:
         L.call("mmb_mm2_stream", *text, *frames, *tail, L.stream_ptr())
+    return num, s, aux
+
+
+def mm2_stream_split_ft(n, t, d, a, vd, audio, visual, ids32, table, wtab32=None, w_dense=None,
+                        flag=None, out=None, s_half: bool = True, colmax=None, colmax_ws=None,
+                        split=None, parts: int = 0):
+    """mm2_stream's `split` route on frames of any FRAME_KINDS dtype
+    (mmb_mm2_stream_split_ft; gathered text only): `audio` / `visual` may both
+    be float16 or both bfloat16 -- a modality in 4-value units from an 8-byte
+    aligned base at a width % 4 == 0, in scalar loads otherwise, never from an
+    odd address -- and the outputs are bit for bit those of
+    mm2_stream(..., split=, parts=) on the same frames upcast to float32.
+    `split` is a split_ws scratch (None: allocated here for `parts`).
+    Returns (x, s, aux)."""
+    kind = frame_kind(audio, visual, "mm2_stream_split_ft")
+    if ids32 is None:
+        raise L.MMBError("mm2_stream_split_ft: gathered text (ids32 + table) only")
+    num, s, aux = _stream_outputs("mm2_stream_split_ft", kind, n, d, a, vd, audio, visual, table, out, s_half,
+                                  colmax_ws)
+    if split is None:
+        split = split_ws(n, t, d, a, vd, audio.device, parts)
+    V = table.shape[0] if table is not None else 0
+    L.call("mmb_mm2_stream_split_ft", L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32), L.ptr(w_dense),
+           L.ptr(audio), L.ptr(visual), FRAME_KINDS[kind][1], n, t, d, a, vd, L.ptr(num), L.ptr(s),
+           int(s_half), L.ptr(aux), L.ptr(flag), L.ptr(colmax), L.ptr(colmax_ws), int(parts), L.ptr(split),
+           split.numel() * split.element_size(), L.stream_ptr())
     return num, s, aux
 
 
@@ -831,7 +866,8 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
               stream_project: bool | None = None, narrow_fused: bool | None = None,
               fork_projection: bool | None = None, split_stream: bool | None = None,
               split_projection: bool = True, frames: str = "f32",
-              fused_frames16: bool = False, narrow_frames16: bool = False) -> StepPlan:
+              fused_frames16: bool = False, narrow_frames16: bool = False,
+              split_frames16: bool = False) -> StepPlan:
     """The plan of a step over `n` of a split's `n_total` utterances on a chip
     of `cus` CUs; the remaining arguments are FusedStep's overrides (None: by
     shape).  Precedence: the fused front kernels need one chunk ASKED for and
@@ -848,13 +884,16 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
     for the narrow fused kernel (mmb_mm2_stream_project_narrow_ft):
     `narrow_fused` then keeps the caller's value and the front is
     "narrow_fused" exactly where the f32 plan of the shape chooses it; with
-    both set the precedence is the f32 plan's.  On f32 frames the keywords
-    change nothing."""
+    both set the precedence is the f32 plan's.  `split_frames16` is the third
+    sibling, for the split stream (mmb_mm2_stream_split_ft): `split_stream`
+    then keeps the caller's value and `split` is set exactly where the f32 plan
+    of the shape sets it.  On f32 frames the keywords change nothing."""
     check_npc(npc)
     if frames not in FRAME_KINDS:
         raise ValueError(f"frames must be one of {', '.join(FRAME_KINDS)}, not {frames!r}")
     if frames != "f32":
-        split_stream = False
+        if not split_frames16:
+            split_stream = False
         if not fused_frames16:
             stream_project = False
         if not narrow_frames16:
@@ -965,7 +1004,9 @@ class FusedStep:
     projection kernel on them where the f32 plan of the shape would choose it
     (mm2_stream_project_ft: no s buffer, the same rows bit for bit as on the
     upcast frames), `narrow_frames16=True` to the narrow fused kernel in the
-    same way (mm2_stream_project_narrow_ft; MOSI's widths).
+    same way (mm2_stream_project_narrow_ft; MOSI's widths), and
+    `split_frames16=True` to the split stream of the two-kernel step
+    (mm2_stream_split_ft; POM's long transcripts).
 
     Which of these a step takes is decided once, by step_plan() (`self.plan`);
     _run is one sequence over it: front kernel, chunk pipeline, projection
@@ -980,7 +1021,7 @@ class FusedStep:
                  narrow_fused: bool | None = None, check_each_run: bool = False,
                  fork_projection: bool | None = None, split_stream: bool | None = None,
                  split_projection: bool = True, fused_frames16: bool = False,
-                 narrow_frames16: bool = False):
+                 narrow_frames16: bool = False, split_frames16: bool = False):
         self.inp = inputs
         self.check_each_run = check_each_run
         self.ids = inputs["ids"]
@@ -1003,7 +1044,7 @@ class FusedStep:
                                   narrow_fused=narrow_fused, fork_projection=fork_projection,
                                   split_stream=split_stream, split_projection=split_projection,
                                   frames=self.frames, fused_frames16=fused_frames16,
-                                  narrow_frames16=narrow_frames16)
+                                  narrow_frames16=narrow_frames16, split_frames16=split_frames16)
         self.proj = MMB2Projection(networks, self.d, self.a, self.vd, self.t, dev)
         kp = self.proj.kp
         self.x = torch.empty((self.n, self.d), dtype=torch.float32, device=dev)
@@ -1121,11 +1162,13 @@ class FusedStep:
     def _stream_chunk(self, c: int):
         r0, r1 = self.bounds[c]
         inp = self.inp
-        mm2_stream(r1 - r0, self.t, self.d, self.a, self.vd, inp["audio"][r0:r1],
-                   inp["visual"][r0:r1], ids32=self.ids[r0:r1], table=self.table,
-                   wtab32=inp["wtab"], flag=self.flag, s_half=self.s_half,
-                   out=(self.x[r0:r1], self.s[r0:r1], self.aux_of(c)),
-                   colmax=self.colmax, colmax_ws=self.colmax_ws, split=self.split)
+        # the split stream on 16-bit frames (split_frames16) has its own mirror
+        stream = mm2_stream_split_ft if self.split is not None and self.frames != "f32" else mm2_stream
+        stream(r1 - r0, self.t, self.d, self.a, self.vd, inp["audio"][r0:r1],
+               inp["visual"][r0:r1], ids32=self.ids[r0:r1], table=self.table,
+               wtab32=inp["wtab"], flag=self.flag, s_half=self.s_half,
+               out=(self.x[r0:r1], self.s[r0:r1], self.aux_of(c)),
+               colmax=self.colmax, colmax_ws=self.colmax_ws, split=self.split)
 
     def _project(self, c: int, pc=None):
         """Chunk c's MMB2 rows; with `pc` also its PC-removed rows."""

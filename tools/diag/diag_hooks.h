@@ -36,7 +36,11 @@ bool diag_wave16_launch(const A& a, int grid, hipStream_t stream);
 template <bool MM2, int VT, int VA, int VV, class A>
 bool diag_stream_small(const A& a, int grid, hipStream_t stream);
 
+template <int VT, int VA, int VV, class FE, class A, class Q>
+bool diag_split16_launch(const A& a, const Q& q, float* part, int64_t grid, hipStream_t stream);
+
 #define MMB_HOOK_STREAM_GRID_MULT diag_stream_grid_mult()
+#define MMB_HOOK_SPLIT16_LAUNCH diag_split16_launch<VT, VA, VV, FE>(a, q, part, grid, stream)
 #define MMB_HOOK_NARROW_VARIANT diag_knob("MMB_STREAM_NARROW", 10)
 #define MMB_HOOK_NARROW_LAUNCH diag_narrow_launch(var, a, grid, stream)
 #define MMB_HOOK_WAVE_LAUNCH diag_wave_launch<MM2, CT, CA, CV>(a, grid, stream)

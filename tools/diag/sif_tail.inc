@@ -56,6 +56,22 @@ bool diag_wave16_launch(const A& a, int grid, hipStream_t stream) {
   return true;
 }
 
+// launch_split on 16-bit frames with MMB_SPLIT16_UNR: frames unrolled per
+// thread group of the frame workgroups (the product runs kSplitFU16; the sums
+// do not depend on it).  Only the all-vector instantiation has the variant:
+// POM's widths, the ones tools/split_ab.py times.
+template <int VT, int VA, int VV, class FE, class A, class Q>
+bool diag_split16_launch(const A& a, const Q& q, float* part, int64_t grid, hipStream_t stream) {
+  if constexpr (VT == 4 && VA == 4 && VV == 4) {
+    const unsigned g = static_cast<unsigned>(grid);
+    switch (diag_knob("MMB_SPLIT16_UNR", kSplitFU16)) {
+      case 8: utt_split_part_kernel<4, 4, 4, 8, kSplitTU, FE><<<g, kNT, 0, stream>>>(a, q, part); return true;
+      case 16: utt_split_part_kernel<4, 4, 4, 16, kSplitTU, FE><<<g, kNT, 0, stream>>>(a, q, part); return true;
+    }
+  }
+  return false;
+}
+
 // launch_stream's few-long-rows branch with MMB_STREAM_SMALL: 0 as large N,
 // 1 the product's 320 x 16 / 8 (returns false), 2 1024 threads x 4 / 4
 template <bool MM2, int VT, int VA, int VV, class A>

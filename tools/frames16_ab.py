@@ -18,6 +18,10 @@ the f32 ones rounded; they live beside them in HBM):
                     the same 16-bit frames with narrow_frames16=True (the
                     narrow fused kernel where the f32 plan takes it,
                     mmb_mm2_stream_project_narrow_ft: MOSI's widths)
+    bf16_split, f16_split
+                    the same 16-bit frames with split_frames16=True (the split
+                    stream where the f32 plan takes it,
+                    mmb_mm2_stream_split_ft: POM's long transcripts)
 
 Per-phase HIP event times, median per variant; for the front kernel of every
 variant its algorithmic HBM bytes per utterance (rows read once,
@@ -25,6 +29,7 @@ outputs written once) and the fraction of the 8 TB/s peak they make.
 
     python tools/frames16_ab.py                      # configs[3]: 1M x 40 x 300 / 300 / 300, V = 400k
     python tools/frames16_ab.py --T 20 --A 76 --Vd 48 --V 3016     # the MOSI shape
+    python tools/frames16_ab.py --n 100 --T 1089 --V 7763          # POM's valid shape (the split stream)
     python tools/frames16_ab.py --unr 6 8    # the tools build (make diag): also the 16-bit wave kernel
                                              # at 6 / 8 frames per load group (the product runs 4)
 """
@@ -99,7 +104,9 @@ def main():
         steps[k + "_fused"] = P.FusedStep(steps[k].inp, nets, fused_frames16=True)
     for k in ("bf16", "f16"):  # and to the narrow fused front
         steps[k + "_narrow"] = P.FusedStep(steps[k].inp, nets, narrow_frames16=True)
-    opted = [k for k in steps if k.endswith(("_fused", "_narrow"))]
+    for k in ("bf16", "f16"):  # and to the split stream
+        steps[k + "_split"] = P.FusedStep(steps[k].inp, nets, split_frames16=True)
+    opted = [k for k in steps if k.endswith(("_fused", "_narrow", "_split"))]
     knob = {k: None for k in steps}
     for u in args.unr:  # the same steps (and buffers), launched at another depth
         for k in ("bf16", "f16"):
