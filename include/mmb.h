@@ -82,6 +82,33 @@ int mmb_sif_wavg(const float* table, int64_t v, int d, const int32_t* ids, int64
                  const float* w, const float* wtab32, float* x_out, float* num_out,
                  float* cnt_out, int32_t* flag, hipStream_t stream);
 
+/* mmb_sif_wavg on a word table kept in 16-bit storage: table [v,d] contiguous
+ * holds elements of table_type.  A table value is widened to f32 in registers
+ * right after its (plain, cached: the rows are the reused data) load -- exact
+ * for both 16-bit types, fp16 subnormals included -- and summed by the
+ * statements of mmb_sif_wavg in their order, the workgroup kernel's row-0
+ * shortcut (w0 E0 entering once) included: x, num and cnt are bit for bit
+ * what mmb_sif_wavg writes for the same table upcast to f32 by the caller.
+ * The library rounds nothing: the caller chose the 16-bit values.  Outputs,
+ * the empty call and the flag bits are mmb_sif_wavg's.
+ * MMB_TABLE_F32 is mmb_sif_wavg itself for the same arguments.
+ * 16-bit table: the wave kernel at l <= 64, d % 4 == 0 and <= 512, table
+ * 8-byte and x_out / num_out 16-byte aligned (a column unit is 4 values = one
+ * 8-byte load); otherwise the workgroup kernel, in 4-value units when
+ * d % 4 == 0 and the table is 8-byte aligned (d up to 1280), in scalar 2-byte
+ * loads if not (d up to 320).
+ * MMB_EINVAL before any launch: a table_type outside 0..2 (also with n == 0),
+ * a 16-bit table that is not 2-byte aligned, null ids, anything mmb_sif_wavg
+ * rejects.
+ * replaces: sif_functions.get_weighted_average /root/reference/sif_functions.py:28-56
+ *   (which reads an f32 table only)                                          */
+#define MMB_TABLE_F32 0
+#define MMB_TABLE_F16 1 /* IEEE binary16 */
+#define MMB_TABLE_BF16 2
+int mmb_sif_wavg_tt(const void* table, int table_type, int64_t v, int d, const int32_t* ids,
+                    int64_t n, int l, const float* w, const float* wtab32, float* x_out,
+                    float* num_out, float* cnt_out, int32_t* flag, hipStream_t stream);
+
 /* ---------------------------------------------------------------- a3 (Gram)
  * g[d,d] (float64, full symmetric) = sum_i x_i x_i^T with x_i = num[i]/cnt[i]
  * (cnt nullable -> x = num).  Products of f32 values are exact in f64 (fp64
@@ -300,6 +327,41 @@ int mmb_mm2_stream_ft(const int32_t* ids, const float* table, int64_t v, const f
                       int64_t n, int t, int d, int a, int vd, float* num_out, void* s_out,
                       int s_half, float* aux_out, int32_t* flag, uint32_t* colmax,
                       void* colmax_ws, hipStream_t stream);
+
+/* mmb_mm2_stream_ft on a word table kept in 16-bit storage as well: table
+ * [v,d] contiguous holds elements of table_type (MMB_TABLE_*, as
+ * mmb_sif_wavg_tt), the frames elements of frame_type; all nine pairs are
+ * taken.  Text is gathered (ids + table, weights from wtab32 or per token from
+ * w_dense).  A table value is widened to f32 in registers right after its
+ * (plain, cached) load -- exact for both 16-bit types, fp16 subnormals
+ * included -- and enters the weighted sum num, the text sums Sx_e / Sxx_e,
+ * the workgroup kernel's row-0 shortcut (row 0 once, as w0 E0, c0 E0,
+ * c0 E0^2) and the column bounds by the statements of mmb_mm2_stream in their
+ * order: x, s (both s_half formats), the three aux planes, the column bounds
+ * and the flag word are bit for bit what mmb_mm2_stream_ft writes for the same
+ * table upcast to f32 by the caller (where that call takes the same kernel: a
+ * 16-bit table never takes the narrow-frame route, whose frame sums are in
+ * another order).  The library rounds nothing.  Outputs, layouts, the empty
+ * call and the flag bits are mmb_mm2_stream's.
+ * MMB_TABLE_F32 is mmb_mm2_stream_ft itself for the same arguments.
+ * 16-bit table: the wave kernel at t <= 64, widths % 4 == 0 and <= 512, table
+ * 8-byte and num_out / s_out 16-byte aligned, the frames aligned to a unit of
+ * their own type (a text column unit is 4 values = one 8-byte load);
+ * otherwise the workgroup kernel, the text in 4-value units when d % 4 == 0
+ * and the table is 8-byte aligned (d up to 1280), in scalar 2-byte loads if
+ * not (d up to 320); the frames follow mmb_mm2_stream_ft's rules for their
+ * type.
+ * MMB_EINVAL before any launch: a table_type outside 0..2 (also with n == 0),
+ * a 16-bit table that is not 2-byte aligned, null ids, anything
+ * mmb_mm2_stream_ft rejects.
+ * replaces the frame loops of sif2.estimate_embedding_overall_gpu2
+ *   /root/reference/sif2.py:181-205 and the gathers at simplesif.py:862-871
+ *   (which read an f32 table only)                                           */
+int mmb_mm2_stream_tt(const int32_t* ids, const void* table, int table_type, int64_t v,
+                      const float* wtab32, const float* w_dense, const void* audio,
+                      const void* visual, int frame_type, int64_t n, int t, int d, int a, int vd,
+                      float* num_out, void* s_out, int s_half, float* aux_out, int32_t* flag,
+                      uint32_t* colmax, void* colmax_ws, hipStream_t stream);
 
 /* mmb_mm2_stream for a few long rows (POM's splits: 100 / 203 transcripts of
  * 1089 / 1357 tokens), split over workgroups: every utterance is cut into P

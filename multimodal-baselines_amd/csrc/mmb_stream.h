@@ -1,6 +1,7 @@
-// What the stream sources share (sif_kernels.hip, narrow_fused_kernels.hip
-// and, through mmb_fused.h, the three fused sources; included by them only): the
-// kernels' argument block and limits, the frame element types, the device
+// What the stream sources share (narrow_fused_kernels.hip, through
+// mmb_stream_kernels.h the three SIF sources and, through mmb_fused.h, the
+// three fused sources; included by them only): the
+// kernels' argument block and limits, the frame and table element types, the device
 // helpers more than one kernel family uses, and the declarations of the entry
 // points' host-side front end (defined once, in sif_kernels.hip).  No
 // __global__ function lives here: every kernel is in exactly one code object.
@@ -99,6 +100,36 @@ __device__ __forceinline__ float4 frame_f32x4(u2 q) {
   }
 }
 
+// Word-table element types of mmb_sif_wavg_tt / mmb_mm2_stream_tt: f32, or
+// the same two 16-bit storage types, widened in the same exact way right
+// after the load -- so a kernel instantiated for a 16-bit table type TE sums
+// what its f32 instantiation sums on the upcast table, bit for bit.
+// StreamArgs::table stays a float pointer; a TE kernel reads it as TE.
+// bytes of a table value of storage type table_type (MMB_TABLE_*, include/mmb.h); 0: not a table type
+inline int table_bytes(int table_type) {
+  return table_type == MMB_TABLE_F32 ? 4 : (table_type == MMB_TABLE_F16 || table_type == MMB_TABLE_BF16) ? 2 : 0;
+}
+// element f of the table as f32 (the workgroup kernels' row-0 shortcut)
+template <class TE>
+__device__ __forceinline__ float table_f32(const float* table, int f) {
+  if constexpr (std::is_same_v<TE, float>) {
+    return table[f];
+  } else {
+    return frame_f32<TE>(reinterpret_cast<const uint16_t*>(table)[f]);
+  }
+}
+// ldv on a 16-bit table row: plain cached loads (the rows are the reused
+// data), a unit of 4 values one 8-byte load, a scalar one a 2-byte load
+template <int VEC, class TE>
+__device__ __forceinline__ void ldv16(const TE* p, float (&v)[VEC]) {
+  if constexpr (VEC == 4) {
+    const float4 q = frame_f32x4<TE>(*reinterpret_cast<const u2*>(p));
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+    v[0] = frame_f32<TE>(*reinterpret_cast<const uint16_t*>(p));
+  }
+}
+
 // the same, non-temporal: for the read-once frame streams (a 16-bit unit of
 // 4 values is one 8-byte load, a scalar one a 2-byte load)
 template <int VEC, class FE>
@@ -178,8 +209,9 @@ __device__ __forceinline__ void stage_token(const StreamArgs& a, int64_t i, int 
 // template argument, so the TU unrolled rows' loads issue together: a
 // runtime `split_emb` test per row put a branch and a wait for that row's
 // load after every load (r06: the gfx950 ISA of the split-part kernel).
-template <bool MM2, bool SPLIT, int VT, int TU>
-__device__ __forceinline__ void text_rows(const float* tsrc, const float* esrc, const int64_t* s_off,
+// TE: the rows' element type (a 16-bit word table: widened after the load).
+template <bool MM2, bool SPLIT, int VT, int TU, class TE = float>
+__device__ __forceinline__ void text_rows(const TE* tsrc, const TE* esrc, const int64_t* s_off,
                                           const float* s_w, int nkeep, int rT, int RT, int cT,
                                           float (&num)[VT], float (&sx)[VT], float (&sxx)[VT]) {
 #pragma unroll TU
@@ -189,10 +221,15 @@ __device__ __forceinline__ void text_rows(const float* tsrc, const float* esrc, 
     const bool ok = off >= 0;
     const int64_t o = ok ? off : 0;
     float v[VT];
-    ldv<VT>(tsrc + o + cT * VT, v);
+    if constexpr (std::is_same_v<TE, float>) {
+      ldv<VT>(tsrc + o + cT * VT, v);
+    } else {
+      ldv16<VT, TE>(tsrc + o + cT * VT, v);
+    }
 #pragma unroll
     for (int e = 0; e < VT; ++e) v[e] = ok ? v[e] : 0.f;
     if constexpr (SPLIT) {
+      static_assert(std::is_same_v<TE, float>, "a second dense tensor is f32");
       float u[VT];
       ldv<VT>(esrc + o + cT * VT, u);
 #pragma unroll
@@ -304,12 +341,12 @@ int stream_args(StreamArgs* s, const int32_t* ids, const float* table, int64_t v
 int empty_call(uint32_t* colmax, int d, hipStream_t stream);
 int reduce_colmax(int rc, const StreamArgs& s, int parts, uint32_t* colmax, hipStream_t stream);
 // vector eligibility of the three modalities: rows of whole 4-value column
-// units from a base aligned to one unit -- 16 bytes of text, 4 * fbytes
-// (frame_bytes) of audio / visual
+// units from a base aligned to one unit -- 4 * tbytes (table_bytes; dense
+// text: 16) of text, 4 * fbytes (frame_bytes) of audio / visual
 struct StreamVec {
   bool t, a, v;
 };
-StreamVec stream_vec(const StreamArgs& s, int fbytes = 4);
+StreamVec stream_vec(const StreamArgs& s, int fbytes = 4, int tbytes = 4);
 bool units_fit(const StreamArgs& s, const StreamVec& vec);
 #pragma GCC visibility pop
 

@@ -30,6 +30,8 @@ MMB_FLAG_SYNC_TIMEOUT = 4
 # frame element types of mmb_mm2_stream_ft, mmb_mm2_stream_split_ft,
 # mmb_mm2_stream_project_ft and mmb_mm2_stream_project_narrow_ft
 MMB_FRAMES_F32, MMB_FRAMES_F16, MMB_FRAMES_BF16 = 0, 1, 2
+# word-table element types of mmb_sif_wavg_tt and mmb_mm2_stream_tt
+MMB_TABLE_F32, MMB_TABLE_F16, MMB_TABLE_BF16 = 0, 1, 2
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -42,6 +44,7 @@ SIGNATURES = {
     "mmb_version": (_I, []),
     "mmb_seq2weight": (_I, [_P, _P, _L, _L, _P, _L, _P, _P, _P]),
     "mmb_sif_wavg": (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mmb_sif_wavg_tt": (_I, [_P, _I, _L, _I, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mmb_gram_workspace_bytes": (_S, [_L, _I]),
     "mmb_gram": (_I, [_P, _P, _L, _I, _P, _I, _P, _P]),
     "mmb_gram_part": (_I, [_P, _P, _L, _L, _I, _I, _P, _P]),
@@ -70,6 +73,8 @@ SIGNATURES = {
     "mmb_mm2_stream": (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _I,
                             _P, _P, _P, _P, _P]),
     "mmb_mm2_stream_ft": (_I, [_P, _P, _L, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _P, _I,
+                               _P, _P, _P, _P, _P]),
+    "mmb_mm2_stream_tt": (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _P, _I,
                                _P, _P, _P, _P, _P]),
     "mmb_mm2_colmax_ws_bytes": (_S, [_I]),
     "mmb_mm2_stream_split_parts": (_I, [_L, _I]),

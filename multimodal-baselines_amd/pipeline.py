@@ -99,22 +99,55 @@ def seq2weight(seq32: torch.Tensor, sel: torch.Tensor | None, wtab64: torch.Tens
     return w
 
 
+# Storage types of the word table: the name step_plan and FusedStep use ->
+# (torch dtype, the table_type of mmb_sif_wavg_tt / mmb_mm2_stream_tt).  The
+# 16-bit kinds are read by the SIF gather and the plain stream kernels only
+# (weighted_sum, sif_embeddings, mm2_stream); nothing here converts a table.
+TABLE_KINDS = {"f32": (torch.float32, L.MMB_TABLE_F32),
+               "f16": (torch.float16, L.MMB_TABLE_F16),
+               "bf16": (torch.bfloat16, L.MMB_TABLE_BF16)}
+_TABLE_KIND_OF = {dtype: kind for kind, (dtype, _) in TABLE_KINDS.items()}  # (one lookup on the eager paths)
+
+
+def table_kind(table: torch.Tensor, who: str = "mm2_stream") -> str:
+    """The TABLE_KINDS name of a word table; MMBError for a dtype the kernels
+    do not read (before any launch: the C ABI takes a bare pointer and would
+    read the bytes as another type, past the end of a narrower buffer)."""
+    kind = _TABLE_KIND_OF.get(table.dtype)
+    if kind is None:
+        raise L.MMBError(f"{who}: the word table must be float32, float16 or bfloat16, not {table.dtype}")
+    return kind
+
+
+def _f32_table(table, who: str) -> None:
+    """The check of every mirror whose kernel reads the table as f32."""
+    if table is not None and table_kind(table, who) != "f32":
+        raise L.MMBError(f"{who} reads a float32 word table only, not {table.dtype}: a 16-bit table "
+                         f"takes mm2_stream (the two-kernel step)")
+
+
 # ------------------------------------------------------------------ a1+a2
 def weighted_sum(table: torch.Tensor, ids32: torch.Tensor, w: torch.Tensor | None = None,
                  wtab32: torch.Tensor | None = None, flag: torch.Tensor | None = None,
                  x_out: bool = False):
-    """Returns (num [N,D], cnt [N]) or x [N,D] (= num/cnt) if x_out."""
+    """Returns (num [N,D], cnt [N]) or x [N,D] (= num/cnt) if x_out.  `table`
+    may be float16 or bfloat16 instead of float32 (mmb_sif_wavg_tt): the
+    outputs are bit for bit those of the same table upcast to float32."""
     n, l = ids32.shape
     V, D = table.shape
     dev = table.device
+    kind = table_kind(table, "weighted_sum")
+    # the entry point and its table arguments: a 16-bit table carries its type
+    entry, tab = (("mmb_sif_wavg", (L.ptr(table),)) if kind == "f32" else
+                  ("mmb_sif_wavg_tt", (L.ptr(table), TABLE_KINDS[kind][1])))
     if x_out:
         x = torch.empty((n, D), dtype=torch.float32, device=dev)
-        L.call("mmb_sif_wavg", L.ptr(table), V, D, L.ptr(ids32), n, l, L.ptr(w), L.ptr(wtab32),
+        L.call(entry, *tab, V, D, L.ptr(ids32), n, l, L.ptr(w), L.ptr(wtab32),
                L.ptr(x), None, None, L.ptr(flag), L.stream_ptr())
         return x
     num = torch.empty((n, D), dtype=torch.float32, device=dev)
     cnt = torch.empty((n,), dtype=torch.float32, device=dev)
-    L.call("mmb_sif_wavg", L.ptr(table), V, D, L.ptr(ids32), n, l, L.ptr(w), L.ptr(wtab32),
+    L.call(entry, *tab, V, D, L.ptr(ids32), n, l, L.ptr(w), L.ptr(wtab32),
            None, L.ptr(num), L.ptr(cnt), L.ptr(flag), L.stream_ptr())
     return num, cnt
 
@@ -324,7 +357,9 @@ def global_pc(num, cnt, npc: int, n_total: int, row0: int = 0, allreduce=None, o
 def sif_embeddings(table, ids, wtab32=None, w=None, npc: int = 1, out_dtype=torch.float32,
                    check_ids: bool = True, allreduce=None, n_total=None, row0: int = 0):
     """a1-a5 fused on device: weighted average, Gram (+ optional all-reduce
-    across ranks), randomized-SVD PC, removal.  Returns (emb [N,D], pc)."""
+    across ranks), randomized-SVD PC, removal.  Returns (emb [N,D], pc).
+    `table` may be float16 or bfloat16 (weighted_sum); everything after the
+    gather works on the f32 rows it writes."""
     ids32 = narrow_ids(ids)
     flag = torch.zeros(1, dtype=torch.int32, device=table.device)
     num, cnt = weighted_sum(table, ids32, w=w, wtab32=wtab32, flag=flag)
@@ -426,7 +461,9 @@ class MMB2Projection:
         token weights from the cache's own copy, so the cache is keyed on BOTH
         tensors (identity here, storage address + version counter in
         refresh_if_changed); writes into them that bump neither (raw-pointer
-        writes by other libmmb kernels, `t.data.copy_`) need invalidate()."""
+        writes by other libmmb kernels, `t.data.copy_`) need invalidate().
+        The cache is built from a float32 table only."""
+        _f32_table(table, "MMB2Projection.enable_text_cache")
         src = getattr(self, "text_src", None)
         if (getattr(self, "text_cache", None) is None or src[0] is not table
                 or src[1] is not wtab32):
@@ -511,21 +548,23 @@ def frame_kind(audio: torch.Tensor, visual: torch.Tensor, who: str = "mm2_stream
     raise L.MMBError(f"{who}: frames must be float32, float16 or bfloat16, not {audio.dtype}")
 
 
-def _stream_outputs(who: str, kind: str, n, d, a, vd, audio, visual, text_src, out, s_half: bool, colmax_ws):
+def _stream_outputs(who: str, kind: str, n, d, a, vd, audio, visual, text_src, out, s_half: bool, colmax_ws,
+                    text_kind: str = "f32"):
     """(x, s, aux) of mm2_stream and mm2_stream_split_ft -- `out` if given,
     else allocated -- after the checks both make before the call: the widths
     against the stream kernels' limits, the s buffer's dtype, the column-bound
-    workspace's size."""
+    workspace's size.  `text_kind`: the TABLE_KINDS name of the text source."""
     # a vector row: whole 4-element units from a base aligned to one unit
-    # (16 bytes of f32; 8 bytes of a 16-bit frame type)
+    # (16 bytes of f32; 8 bytes of a 16-bit frame or table type)
     unit = 16 if kind == "f32" else 8
-    for what, w, src, al in (("text", d, text_src, 16), ("audio", a, audio, unit),
+    text_unit = 16 if text_kind == "f32" else 8
+    for what, w, src, al in (("text", d, text_src, text_unit), ("audio", a, audio, unit),
                              ("visual", vd, visual, unit)):
         vec = w % 4 == 0 and src is not None and src.data_ptr() % al == 0
         if w > (STREAM_MAX_VECTOR_WIDTH if vec else STREAM_MAX_SCALAR_WIDTH):
             raise L.MMBError(f"{who}: {what} width {w} is past the stream kernels' limit: "
                              f"{STREAM_MAX_VECTOR_WIDTH} for rows of whole float4 units (width % 4 "
-                             f"== 0, 16-byte aligned; 8-byte for 16-bit frames), "
+                             f"== 0, 16-byte aligned; 8-byte for 16-bit frames or a 16-bit table), "
                              f"{STREAM_MAX_SCALAR_WIDTH} otherwise")
     if out is None:
         dev = audio.device
@@ -555,15 +594,25 @@ def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=Non
     `audio` / `visual` may both be float16 or both bfloat16 instead of float32
     (mmb_mm2_stream_ft; gathered text, no `split`): the outputs are bit for bit
     those of the same frames upcast to float32 (with `split`:
-    mm2_stream_split_ft)."""
+    mm2_stream_split_ft).
+
+    `table` may be float16 or bfloat16 instead of float32 (mmb_mm2_stream_tt;
+    gathered text, no `split`, frames of any of the three dtypes): the outputs
+    are bit for bit those of the same table upcast to float32."""
     kind = frame_kind(audio, visual)
+    tkind = table_kind(table) if table is not None else "f32"
     if kind != "f32" and ids32 is None:
         raise L.MMBError(f"mm2_stream: {kind} frames go with gathered text (ids32 + table) only")
     if kind != "f32" and split is not None:
         raise L.MMBError(f"mm2_stream: the split stream reads float32 frames only, not {kind}")
+    if tkind != "f32" and ids32 is None:
+        raise L.MMBError(f"mm2_stream: a {tkind} word table goes with gathered text (ids32 + table) only; "
+                         f"dense text is float32 and reads no table")
+    if tkind != "f32" and split is not None:
+        raise L.MMBError(f"mm2_stream: the split stream reads a float32 word table only, not {tkind}")
     text_src = table if ids32 is not None else text_dense
     num, s, aux = _stream_outputs("mm2_stream", kind, n, d, a, vd, audio, visual, text_src, out, s_half,
-                                  colmax_ws)
+                                  colmax_ws, text_kind=tkind)
     V = table.shape[0] if table is not None else 0
     # the arguments the three entry points share: the gathered text's, the
     # frames', and everything from the shapes on
@@ -575,6 +624,9 @@ def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=Non
     if split is not None:
         L.call("mmb_mm2_stream_split", *text, *frames, *tail, int(parts), L.ptr(split),
                split.numel() * split.element_size(), L.stream_ptr())
+    elif tkind != "f32":
+        L.call("mmb_mm2_stream_tt", L.ptr(ids32), L.ptr(table), TABLE_KINDS[tkind][1], V, L.ptr(wtab32),
+               L.ptr(w_dense), *frames, FRAME_KINDS[kind][1], *tail, L.stream_ptr())
     elif kind != "f32":
         L.call("mmb_mm2_stream_ft", *gathered, L.ptr(w_dense), *frames, FRAME_KINDS[kind][1], *tail,
                L.stream_ptr())
@@ -597,6 +649,7 @@ def mm2_stream_split_ft(n, t, d, a, vd, audio, visual, ids32, table, wtab32=None
     kind = frame_kind(audio, visual, "mm2_stream_split_ft")
     if ids32 is None:
         raise L.MMBError("mm2_stream_split_ft: gathered text (ids32 + table) only")
+    _f32_table(table, "mm2_stream_split_ft")
     num, s, aux = _stream_outputs("mm2_stream_split_ft", kind, n, d, a, vd, audio, visual, table, out, s_half,
                                   colmax_ws)
     if split is None:
@@ -646,6 +699,7 @@ def _stream_project(entry: str, ft: bool, cache: bool, text: tuple, n, t, d, a, 
     text cache, else only its weight pieces; `text`: the entry point's own
     text arguments, between wtab32 (or the text cache) and audio."""
     kind = frame_kind(audio, visual, entry)
+    _f32_table(table, entry)
     if not ft and kind != "f32":
         raise L.MMBError(f"{entry} reads float32 frames only, not {audio.dtype}: 16-bit frames "
                          f"take mm2_stream (the two-kernel step)")
@@ -867,7 +921,7 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
               fork_projection: bool | None = None, split_stream: bool | None = None,
               split_projection: bool = True, frames: str = "f32",
               fused_frames16: bool = False, narrow_frames16: bool = False,
-              split_frames16: bool = False) -> StepPlan:
+              split_frames16: bool = False, table: str = "f32") -> StepPlan:
     """The plan of a step over `n` of a split's `n_total` utterances on a chip
     of `cus` CUs; the remaining arguments are FusedStep's overrides (None: by
     shape).  Precedence: the fused front kernels need one chunk ASKED for and
@@ -887,10 +941,20 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
     both set the precedence is the f32 plan's.  `split_frames16` is the third
     sibling, for the split stream (mmb_mm2_stream_split_ft): `split_stream`
     then keeps the caller's value and `split` is set exactly where the f32 plan
-    of the shape sets it.  On f32 frames the keywords change nothing."""
+    of the shape sets it.  On f32 frames the keywords change nothing.
+    A 16-bit word `table` ("f16" / "bf16", TABLE_KINDS) is read by the plain
+    stream kernel only: `stream_project`, `narrow_fused` and `split_stream`
+    are off whatever the overrides and the three `*_frames16` opt-ins say, so
+    the plan is the two-kernel plan of the shape; with "f32" every plan is as
+    described above.  The table kind is not a field of the plan."""
     check_npc(npc)
     if frames not in FRAME_KINDS:
         raise ValueError(f"frames must be one of {', '.join(FRAME_KINDS)}, not {frames!r}")
+    if table not in TABLE_KINDS:
+        raise ValueError(f"table must be one of {', '.join(TABLE_KINDS)}, not {table!r}")
+    if table != "f32":
+        stream_project = narrow_fused = split_stream = False
+        fused_frames16 = narrow_frames16 = split_frames16 = False
     if frames != "f32":
         if not split_frames16:
             split_stream = False
@@ -1008,6 +1072,11 @@ class FusedStep:
     `split_frames16=True` to the split stream of the two-kernel step
     (mm2_stream_split_ft; POM's long transcripts).
 
+    A 16-bit word table (float16 / bfloat16 `inputs["table"]`, `self.table_kind`)
+    takes the two-kernel step whatever the overrides and opt-ins say
+    (mmb_mm2_stream_tt: the same rows bit for bit as on the upcast table), with
+    frames of any of the three dtypes.
+
     Which of these a step takes is decided once, by step_plan() (`self.plan`);
     _run is one sequence over it: front kernel, chunk pipeline, projection
     (unless the front kernel or the removal carries it), Gram, PC solve,
@@ -1038,13 +1107,16 @@ class FusedStep:
         # the frames' storage type, checked here: a step never launches on a
         # dtype its kernels would read as another
         self.frames = frame_kind(inputs["audio"], inputs["visual"], "FusedStep")
+        # the word table's, likewise: a 16-bit table takes the two-kernel step
+        self.table_kind = table_kind(self.table, "FusedStep")
         self.plan = p = step_plan(self.n, self.n_total, self.t, self.d, self.a, self.vd, self.V, npc,
                                   L.cu_count(dev), chunks=chunks, fuse_remove=fuse_remove,
                                   gram_kind=gram_kind, stream_project=stream_project,
                                   narrow_fused=narrow_fused, fork_projection=fork_projection,
                                   split_stream=split_stream, split_projection=split_projection,
                                   frames=self.frames, fused_frames16=fused_frames16,
-                                  narrow_frames16=narrow_frames16, split_frames16=split_frames16)
+                                  narrow_frames16=narrow_frames16, split_frames16=split_frames16,
+                                  table=self.table_kind)
         self.proj = MMB2Projection(networks, self.d, self.a, self.vd, self.t, dev)
         kp = self.proj.kp
         self.x = torch.empty((self.n, self.d), dtype=torch.float32, device=dev)
