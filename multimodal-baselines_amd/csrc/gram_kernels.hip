@@ -1102,6 +1102,7 @@ extern "C" int mmb_gram(const float* num, const float* cnt, int64_t n, int d, do
 extern "C" int mmb_colmax(const float* x, int64_t n, int d, uint32_t* colmax, int accumulate,
                           hipStream_t stream) {
   MMB_REQUIRE(x && colmax && n >= 0 && d > 0);
+  MMB_REQUIRE(ceil_div(n, 256) <= kMaxGridX);  // a workgroup per 256 rows
   if (!accumulate) {
     const hipError_t e = static_cast<hipError_t>(zero_words_async(colmax, static_cast<int64_t>(sizeof(uint32_t) * d) / 4, stream));
     if (e != hipSuccess) return static_cast<int>(e);

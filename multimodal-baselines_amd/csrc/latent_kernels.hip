@@ -456,6 +456,7 @@ extern "C" int mmb_word_logprob_forward(const float* latents, int64_t b, int d, 
   MMB_REQUIRE(latents && wn && w && mask && lp && ws && b >= 0 && d > 0 && d <= kWordMaxD && v > 0 && l >= 0);
   MMB_REQUIRE(ids ? (table != nullptr) : (sent_dense != nullptr || l == 0));
   MMB_REQUIRE(!want_grad || (state && gsum && cos_out));
+  MMB_REQUIRE(b <= kMaxGridX);  // word_finish_kernel: a workgroup per latent
   if (b == 0) return MMB_OK;
   const int Dp = pad16(d);
   const int S = word_splits(b, v);
@@ -487,6 +488,7 @@ extern "C" int mmb_word_logprob_backward(const float* latents, int64_t b, int d,
                                          float* dlat, hipStream_t stream) {
   MMB_REQUIRE(latents && w && mask && state && gsum && cosv && dlp && dlat && d > 0 && d <= kWordMaxD);
   MMB_REQUIRE(ids ? (table != nullptr) : (sent_dense != nullptr || l == 0));
+  MMB_REQUIRE(b <= kMaxGridX);  // a workgroup per latent
   if (b == 0) return MMB_OK;
   TokSrc tok{ids, table, sent_dense, v};
   word_backward_kernel<<<static_cast<unsigned>(b), 256, 0, stream>>>(
@@ -508,7 +510,8 @@ extern "C" int mmb_gauss_stats(const float* x, const float* mask, int64_t n, int
 
 static int gauss_args(GaussArgs& g, const double* const* stats, const int* fm, const int64_t* idx,
                       int64_t b, int nkeys, const int* mods) {
-  MMB_REQUIRE(stats && fm && mods && nkeys >= 1 && nkeys <= kMaxKeys && b >= 0);
+  // (b: a workgroup per row and key in both Gaussian kernels)
+  MMB_REQUIRE(stats && fm && mods && nkeys >= 1 && nkeys <= kMaxKeys && b >= 0 && b <= kMaxGridX);
   for (int m = 0; m < 3; ++m) {
     g.stats[m] = stats[m];
     g.Fm[m] = fm[m];

@@ -742,6 +742,7 @@ extern "C" int mmb_mlp_forward(const float* latents, const int64_t* idx, int64_t
   MMB_REQUIRE(latents && w1 && b1 && w2 && b2 && y_out && b >= 0 && d > 0 && h > 0 && o > 0);
   if (b == 0) return MMB_OK;
   const int B = 32;
+  MMB_REQUIRE(ceil_div(b, B) <= kMaxGridX);  // a workgroup per batch of rows
   mlp_eval_kernel<<<static_cast<int>(ceil_div(b, B)), 256, sizeof(float) * (d + h), stream>>>(
       latents, nullptr, idx, b, B, d, h, o, w1, b1, w2, b2, nullptr, y_out);
   MMB_LAUNCH_CHECK();
@@ -753,6 +754,7 @@ extern "C" int mmb_mlp_eval(const float* latents, const float* labels, const int
                             const float* b1, const float* w2, const float* b2, float* batch_loss,
                             float* pred_out, hipStream_t stream) {
   MMB_REQUIRE(latents && labels && w1 && b1 && w2 && b2 && n >= 0 && batch > 0 && d > 0 && h > 0 && o > 0);
+  MMB_REQUIRE(ceil_div(n, batch) <= kMaxGridX);  // a workgroup per batch
   if (n == 0) return MMB_OK;
   mlp_eval_kernel<<<static_cast<int>(ceil_div(n, batch)), 256, sizeof(float) * (d + h), stream>>>(
       latents, labels, perm, n, batch, d, h, o, w1, b1, w2, b2, batch_loss, pred_out);
@@ -824,6 +826,7 @@ extern "C" int mmb_mlp_forward_train(const float* x, int64_t b, int d, int h, in
   if (b == 0) return MMB_OK;
   const size_t lds = sizeof(float) * kMlpRows * (d + h);
   MMB_REQUIRE(lds <= 64 * 1024);
+  MMB_REQUIRE(ceil_div(b, kMlpRows) <= kMaxGridX);  // a workgroup per kMlpRows rows
   const int grid = static_cast<int>(ceil_div(b, kMlpRows));
   const size_t lds_w = lds + sizeof(float) * static_cast<size_t>(h) * mlp_wld(d);
   if (d % 4 == 0 && aligned16(w1) && lds_w <= 160 * 1024) {
@@ -857,6 +860,7 @@ extern "C" int mmb_mlp_backward(const float* x, const float* hid, int64_t b, int
   constexpr int kBwdRows = 2;
   const size_t lds = sizeof(float) * kBwdRows * h;
   MMB_REQUIRE(lds <= 64 * 1024);
+  MMB_REQUIRE(ceil_div(b, kBwdRows) <= kMaxGridX);  // a workgroup per kBwdRows rows
   mlp_bwd_rows_kernel<kBwdRows><<<static_cast<int>(ceil_div(b, kBwdRows)), 256, lds, stream>>>(
       hid, b, d, h, o, w1, w2, dy, dh_ws, dx);
   MMB_LAUNCH_CHECK();

@@ -1150,6 +1150,7 @@ static int x3_operands(const void* s_split, const float* num, const float* aux, 
                        const double* pc, const float* sif_out, X3Operands* o) {
   MMB_REQUIRE(s_split && num && aux && wsplit && c0 && out && n >= 0 && d > 0);
   MMB_REQUIRE(ldw == mmb_mm2_ldw(d) && k % 32 == 0 && k >= 32);
+  MMB_REQUIRE(ceil_div(n, kXM) <= kMaxGridX);  // a workgroup per kXM-row tile
   MMB_REQUIRE((pc == nullptr) == (sif_out == nullptr));
   MMB_REQUIRE(aligned16(s_split) && aligned16(wsplit));
   o->s = static_cast<const _Float16*>(s_split);
@@ -1239,6 +1240,7 @@ extern "C" int mmb_mm2_project(const float* s, const float* num, const float* au
                                int d, float* out, hipStream_t stream) {
   MMB_REQUIRE(s && num && aux && wm && c0 && out && n >= 0 && d > 0);
   MMB_REQUIRE(ldw == mmb_mm2_ldw(d) && ldw <= kProjectMaxLdw && k % 32 == 0);
+  MMB_REQUIRE(ceil_div(n, kPM) <= kMaxGridX);  // a workgroup per kPM-row tile
   if (n == 0) return MMB_OK;
   switch (ldw / 64) {
     case 1: return launch_project<1>(s, num, aux, wm, c0, n, k, d, out, stream);

@@ -135,6 +135,12 @@ __host__ __device__ constexpr int x3_swz(int r) { return (0x78 >> (2 * ((r >> 2)
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Largest grid x: an entry point whose grid grows with its rows (a workgroup
+// per row or per block of rows, no grid-stride loop) refuses more with
+// MMB_EINVAL before any launch -- cast to the launch's 32-bit grid, a larger
+// count would wrap and the launch would silently cover a part of the rows.
+constexpr int64_t kMaxGridX = (int64_t{1} << 31) - 1;
+
 // 16-byte alignment: what every float4 / b128 access of a row base needs
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

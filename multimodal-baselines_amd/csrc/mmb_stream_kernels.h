@@ -715,6 +715,7 @@ static int stream_route(StreamArgs& s, uint32_t* colmax, hipStream_t stream) {
     return reduce_colmax(rc, s, parts, colmax, stream);
   }
   MMB_REQUIRE(units_fit(s, vec));
+  MMB_REQUIRE(!s_half || s.N <= kMaxGridX);  // split_rows: a workgroup per row
   s.s_half = 0;  // fp32 sums; split_rows makes them fp16 hi | lo afterwards
   int rc = dispatch3(vec.t, vec.a, vec.v, [&](auto vt, auto va, auto vv) {
     return launch_stream<true, vt.value ? 4 : 1, va.value ? 4 : 1, vv.value ? 4 : 1, FE, TE>(s, stream, &parts);

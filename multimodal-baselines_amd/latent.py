@@ -85,6 +85,7 @@ class _WordLogProb(torch.autograd.Function):
             raise ValueError(f"latent width {D} != word-table width {table.D}")
         Lt = w.shape[1]
         dev = lat.device
+        L.check_grid("word_log_prob", B)
         want = bool(ctx.needs_input_grad[0])
         ws = torch.empty(max(L.query("mmb_word_workspace_bytes", B, D, table.V), 16),
                          dtype=torch.uint8, device=dev)
@@ -169,6 +170,7 @@ class _GaussLogProb(torch.autograd.Function):
         mus, ldm = zip(*[_rows(m) for m in musig[:K]])
         sigs, lds = zip(*[_rows(s) for s in musig[K:]])
         B = mus[0].shape[0]
+        L.check_grid("gauss_log_prob", B)
         lp = torch.empty((K, B), dtype=torch.float32, device=mus[0].device)
         st = _ptr_array(gs.stats)
         fm = (ctypes.c_int * 3)(*gs.fm)

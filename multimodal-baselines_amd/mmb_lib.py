@@ -182,6 +182,18 @@ def query(name, *args):
     return getattr(load(), name)(*args)
 
 
+MAX_GRID_X = 2 ** 31 - 1  # kMaxGridX (csrc/mmb_common.h)
+
+
+def check_grid(who: str, rows: int, per_workgroup: int = 1):
+    """The mirrors' statement of the library's kMaxGridX guard: an entry point
+    that launches a workgroup per `per_workgroup` rows takes at most (2^31 - 1)
+    workgroups per call (MMB_EINVAL before any launch past that)."""
+    if -(-int(rows) // per_workgroup) > MAX_GRID_X:
+        raise MMBError(f"{who}: {rows} rows are past the limit of (2^31 - 1) x {per_workgroup} rows per call "
+                       f"(a workgroup per {per_workgroup} row(s), 2^31 - 1 workgroups per launch); split the call")
+
+
 def require_gpu() -> torch.device:
     if not torch.cuda.is_available():
         raise MMBError("libmmb computes on an MI355X (gfx950) GPU and has no CPU fallback; "

@@ -181,6 +181,7 @@ def colmax(x: torch.Tensor, out: torch.Tensor | None = None, accumulate: bool = 
     """Column bounds max_i |x[i, j]| as float bits (int32 view of uint32) for
     the int8 Gram (mmb_colmax)."""
     n, d = x.shape
+    L.check_grid("colmax", n, 256)
     if out is None:
         out = torch.empty((d,), dtype=torch.int32, device=x.device)
     L.call("mmb_colmax", L.ptr(x), n, d, L.ptr(out), int(accumulate), L.stream_ptr())
@@ -611,6 +612,8 @@ def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=Non
     if tkind != "f32" and split is not None:
         raise L.MMBError(f"mm2_stream: the split stream reads a float32 word table only, not {tkind}")
     text_src = table if ids32 is not None else text_dense
+    if s_half:  # (the workgroup route's fp16 pass: a workgroup per row)
+        L.check_grid("mm2_stream", n)
     num, s, aux = _stream_outputs("mm2_stream", kind, n, d, a, vd, audio, visual, text_src, out, s_half,
                                   colmax_ws, text_kind=tkind)
     V = table.shape[0] if table is not None else 0
@@ -808,6 +811,7 @@ def mm2_project(s, num, aux, proj: MMB2Projection, out=None, pc=None, sif_out=No
     (project_split_ws) a few rows' K loop runs over several workgroups per
     row tile (mmb_mm2_project_x3_split, fp16 s)."""
     n = num.shape[0]
+    L.check_grid("mm2_project", n, 128 if s.dtype == torch.float16 else 64)
     if out is None:
         out = torch.empty((n, proj.d), dtype=torch.float32, device=num.device)
     if pc is not None and (s.dtype != torch.float16 or pc.shape[0] != 1 or sif_out is None):

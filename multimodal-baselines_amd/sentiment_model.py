@@ -76,6 +76,7 @@ class _Regressor(torch.autograd.Function):
         x = x.detach().contiguous()
         b, d = x.shape
         h, o = w1.shape[0], w2.shape[0]
+        L.check_grid("SentimentModel", b, 2)  # (the backward's rows per workgroup; the forward takes 8)
         y = torch.empty((b, o), dtype=torch.float32, device=x.device)
         hid = torch.empty((b, h), dtype=torch.float32, device=x.device)
         L.call("mmb_mlp_forward_train", L.ptr(x), b, d, h, o, L.ptr(w1.detach()),
@@ -127,6 +128,7 @@ class SentimentModel(nn.Module):
         x = x.reshape(-1, x.shape[-1]).contiguous()
         d, h, o = _dims(self)
         w1, b1, w2, b2 = _params(self)
+        L.check_grid("SentimentModel", x.shape[0], 32)
         y = torch.empty((x.shape[0], o), dtype=torch.float32, device=dev)
         with torch.no_grad():
             L.call("mmb_mlp_forward", L.ptr(x), None, x.shape[0], d, h, o, L.ptr(w1), L.ptr(b1),
@@ -202,6 +204,7 @@ def _evaluate(loader, model, latents, dev):
     lab = _labels(loader, dev)
     lat = latents.detach().to(dev, torch.float32).contiguous()
     nb = len(batches)
+    L.check_grid("evaluate", n, loader.batch_size)
     bl = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
     pred = torch.empty((max(n, 1), o), dtype=torch.float32, device=dev)
     L.call("mmb_mlp_eval", L.ptr(lat), L.ptr(lab), L.ptr(perm), n, loader.batch_size, d, h, o,

@@ -160,6 +160,17 @@ ENTRY_ARGS = {
     "mmb_mm2_project_x3_rmpc": "s_split num aux wsplit ldw c0 n k d out pc sif_out stream".split(),
     "mmb_mm2_project_x3_split": ("s_split num aux wsplit ldw c0 n k d out pc sif_out slices ws ws_bytes "
                                  "stream").split(),
+    "mmb_layer_norm_backward": "dy x mean rstd gamma n d dx dgamma dbeta stream".split(),
+    "mmb_mm2_project": "s num aux wm ldw c0 n k d out stream".split(),
+    "mmb_colmax": "x n d colmax accumulate stream".split(),
+    "mmb_mlp_forward": "latents idx b d h o w1 b1 w2 b2 y_out stream".split(),
+    "mmb_mlp_eval": "latents labels perm n batch d h o w1 b1 w2 b2 batch_loss pred_out stream".split(),
+    "mmb_mlp_forward_train": "x b d h o w1 b1 w2 b2 y_out hid_out stream".split(),
+    "mmb_mlp_backward": "x hid b d h o w1 w2 dy dh_ws dx dw1 db1 dw2 db2 stream".split(),
+    "mmb_word_logprob_forward": ("latents b d wn v ids table sent_dense l w mask a want_grad ws lp state gsum "
+                                 "cos_out stream").split(),
+    "mmb_word_logprob_backward": ("latents b d v ids table sent_dense l w mask a state gsum cosv dlp dlat "
+                                  "stream").split(),
 }
 # a valid gathered-text call of each kind (n > 0: it would go on to launch)
 GATHER = dict(ids=P, table=P, v=1000, wtab32=P, text_dense=None, emb_dense=None, w_dense=None, audio=P,
@@ -179,6 +190,17 @@ X3 = dict(s_split=P, num=P, aux=P, wsplit=P, ldw=320, c0=P, n=100, k=1824, d=300
           sif_out=None, slices=2, ws=P, ws_bytes=1 << 40, stream=None)  # slices = 0 asks the device
 for _name in ("mmb_mm2_project_x3", "mmb_mm2_project_x3_rmpc", "mmb_mm2_project_x3_split"):
     BASE[_name] = X3
+BASE["mmb_layer_norm_backward"] = dict(dy=P, x=P, mean=P, rstd=P, gamma=P, n=100, d=300, dx=P, dgamma=P, dbeta=P,
+                                       stream=None)
+MLP = dict(latents=P, x=P, hid=P, idx=None, labels=P, perm=None, b=100, n=100, batch=32, d=300, h=100, o=1, w1=P,
+           b1=P, w2=P, b2=P, y_out=P, hid_out=P, batch_loss=P, pred_out=P, dy=P, dh_ws=P, dx=P, dw1=P, db1=P,
+           dw2=P, db2=P, stream=None)
+WORD = dict(latents=P, b=64, d=300, wn=P, v=3016, ids=P, table=P, sent_dense=None, l=20, w=P, mask=P, a=1e-3,
+            want_grad=1, ws=P, lp=P, state=P, gsum=P, cos_out=P, cosv=P, dlp=P, dlat=P, stream=None)
+BASE.update({"mmb_mm2_project": dict(X3, s=P, wm=P), "mmb_colmax": dict(x=P, n=100, d=300, colmax=P, accumulate=0,
+                                                                      stream=None),
+             "mmb_mlp_forward": MLP, "mmb_mlp_eval": MLP, "mmb_mlp_forward_train": MLP, "mmb_mlp_backward": MLP,
+             "mmb_word_logprob_forward": WORD, "mmb_word_logprob_backward": WORD})
 DENSE = dict(ids=None, table=None, v=0, wtab32=None, text_dense=P, emb_dense=P, w_dense=P)
 BOUNDS = dict(colmax=P, colmax_ws=P)
 EINVAL, OK = -1, 0
@@ -223,6 +245,53 @@ for _name in ("mmb_mm2_project_x3", "mmb_mm2_project_x3_rmpc", "mmb_mm2_project_
 CASES += [(name, "n 0", dict(n=0), OK) for name in ("mmb_sif_wavg", "mmb_mm2_stream", "mmb_mm2_stream_project",
                                                     "mmb_mm2_stream_project_narrow")]
 CASES.append(("mmb_mm2_stream_split", "n 0, no workspace", dict(n=0, parts=0, ws=None, ws_bytes=0), OK))
+# the host guards of 32-bit grids and row indices, on their refused side (the
+# accepted side of each would go on to launch: tests/test_gpu_large.py where a
+# device can hold it).  The workspaces are claimed large enough, so the size
+# check before each guard passes and the guard itself answers.
+HUGE_WS = 1 << 62
+CASES += [
+    # rows are 32-bit in the narrow fused kernel: n < 2^31 - 32 (one batch of rows past the last)
+    ("mmb_mm2_stream_project_narrow", "n 2^31 - 32", dict(n=2 ** 31 - 32), EINVAL),
+    # t = 40 in 2 parts: Pt + 2 Pf = 6 workgroups per row; the grid n (Pt + 2 Pf) <= 2^31 - 1
+    ("mmb_mm2_stream_split", "grid past 2^31 - 1", dict(n=(2 ** 31 - 1) // 6 + 1, ws_bytes=HUGE_WS), EINVAL),
+    # 128-row tiles in 2 slices: tiles nsl <= 2^31 - 1
+    ("mmb_mm2_project_x3_split", "grid past 2^31 - 1", dict(n=128 * 2 ** 30 + 1, ws_bytes=HUGE_WS), EINVAL),
+    # LayerNorm backward: n <= 2^33, and rb + cb < 2^31 blocks (rb = ceil(n / 4) row blocks, cb =
+    # ceil(d / 64) column blocks where dgamma or dbeta is asked for)
+    ("mmb_layer_norm_backward", "n 2^33 + 1", dict(n=2 ** 33 + 1), EINVAL),
+    ("mmb_layer_norm_backward", "rb + cb = 2^31 + 4", dict(n=4 * (2 ** 31 - 1)), EINVAL),
+    ("mmb_layer_norm_backward", "rb = 2^31", dict(n=2 ** 33, dgamma=None, dbeta=None), EINVAL),
+    ("mmb_layer_norm_backward", "n 0, no column sums", dict(n=0, dgamma=None, dbeta=None), OK),
+    # kMaxGridX (csrc/mmb_common.h): a workgroup per row, or per block of rows, and no grid-stride
+    # loop -- 2^31 workgroups are refused where the cast to the launch's grid would wrap
+    ("mmb_mm2_stream", "workgroup route, fp16 s, n 2^31", dict(t=65, n=2 ** 31), EINVAL),
+    ("mmb_mm2_project", "2^31 tiles of 64 rows", dict(n=64 * 2 ** 31), EINVAL),
+    ("mmb_mm2_project_x3", "2^31 tiles of 128 rows", dict(n=128 * 2 ** 31), EINVAL),
+    ("mmb_colmax", "2^31 blocks of 256 rows", dict(n=256 * 2 ** 31), EINVAL),
+    ("mmb_mlp_forward", "2^31 batches of 32 rows", dict(b=32 * 2 ** 31), EINVAL),
+    ("mmb_mlp_eval", "2^31 batches", dict(n=2 ** 31, batch=1), EINVAL),
+    ("mmb_mlp_forward_train", "2^31 blocks of 8 rows", dict(b=8 * 2 ** 31), EINVAL),
+    ("mmb_mlp_backward", "2^31 blocks of 2 rows", dict(b=2 * 2 ** 31), EINVAL),
+    ("mmb_word_logprob_forward", "b 2^31", dict(b=2 ** 31), EINVAL),
+    ("mmb_word_logprob_backward", "b 2^31", dict(b=2 ** 31), EINVAL),
+]
+
+
+def test_gauss_rows_past_the_grid_are_rejected_without_gpu():
+    """mmb_gauss_loglik / _backward launch a workgroup per row and key: 2^31 rows are refused."""
+    import ctypes
+
+    arr = lambda t, *v: (t * len(v))(*v)
+    head = [arr(ctypes.c_void_p, P, 0, 0), arr(ctypes.c_int, 4, 0, 0), None, 2 ** 31, 1, arr(ctypes.c_int, 1),
+            arr(ctypes.c_void_p, P), arr(ctypes.c_void_p, P)]
+    with pytest.raises(mmb_lib.MMBError, match=r"code -1 \(invalid argument\)"):
+        mmb_lib.call("mmb_gauss_loglik", *head, P, None)
+    with pytest.raises(mmb_lib.MMBError, match=r"code -1 \(invalid argument\)"):
+        mmb_lib.call("mmb_gauss_backward", *head, P, arr(ctypes.c_void_p, P), arr(ctypes.c_void_p, P), None)
+    with pytest.raises(mmb_lib.MMBError, match="2\\^31 - 1"):
+        mmb_lib.check_grid("gauss_log_prob", 2 ** 31)
+    mmb_lib.check_grid("colmax", 256 * (2 ** 31 - 1), 256)
 
 
 def test_case_table_starts_from_valid_calls():
