@@ -468,6 +468,40 @@ int mmb_mm2_stream_project_ft(const int32_t* ids, const float* table, int64_t v,
                               float* aux_out, float* mmb2_out, int32_t* flag, uint32_t* colmax,
                               void* colmax_ws, hipStream_t stream);
 
+/* mmb_mm2_stream_project_ft on a word table kept in 16-bit storage as well:
+ * table [v,d] contiguous holds elements of table_type (MMB_TABLE_*, as
+ * mmb_mm2_stream_tt), the frames elements of frame_type; all nine pairs are
+ * taken.  Text is gathered (ids + table, weights from wtab32 or per token
+ * from w_dense).  A 16-bit column unit of a gathered row is one 8-byte
+ * (plain, cached: the rows are the reused data) load and stays packed until
+ * the row is summed; the widening to f32 there is exact for both 16-bit
+ * types, fp16 subnormals included, and the sums are the statements of the
+ * f32-table kernel in their order: every output -- x, the three aux planes,
+ * the MMB2 rows, the column bounds and the flag word -- is bit for bit what
+ * mmb_mm2_stream_project_ft writes for the same table upcast to f32 by the
+ * caller, for each frame type.  The library rounds nothing: the caller chose
+ * the 16-bit values.  Shapes, outputs, layouts, the empty call (n == 0) and
+ * the flag bits are mmb_mm2_stream_project_ft's; like it the call never
+ * synchronises, never allocates and can be captured into a graph.  The
+ * pipelined streamers address the table through one buffer descriptor, so a
+ * table of v d sizeof(element) >= 2^31 bytes takes the group-at-a-time
+ * streamer (the same rows): a 16-bit table keeps the pipelined one up to
+ * twice the rows of an f32 table.
+ * MMB_TABLE_F32 is mmb_mm2_stream_project_ft itself for the same arguments.
+ * MMB_EINVAL before any launch: a table_type or frame_type outside 0..2 (also
+ * with n == 0), null ids, a 16-bit table base that is not 8-byte aligned
+ * (num_out / wpieces stay 16-byte aligned, the frames aligned to a unit of
+ * their own type), anything mmb_mm2_stream_project_ft rejects.
+ * replaces: the frame loops and projections of sif2.estimate_embedding_overall_gpu2
+ *   /root/reference/sif2.py:164-208 and the gathers at simplesif.py:862-871
+ *   (which read an f32 table and f32 frames only)                            */
+int mmb_mm2_stream_project_tt(const int32_t* ids, const void* table, int table_type, int64_t v,
+                              const float* wtab32, const float* w_dense, const void* audio,
+                              const void* visual, int frame_type, int64_t n, int t, int d, int a,
+                              int vd, const void* wpieces, const float* c0, float* num_out,
+                              float* aux_out, float* mmb2_out, int32_t* flag, uint32_t* colmax,
+                              void* colmax_ws, hipStream_t stream);
+
 /* mmb_mm2_project_x3_rmpc for a few rows (the dataset splits: 100-1,284
  * rows put one or a few workgroups through the whole K loop), split over K:
  * slices (0: mmb_mm2_project_x3_split_slices) workgroups per 128-row tile

@@ -1,7 +1,9 @@
 // The MMB2 stream and its projection in one kernel (mmb_fused.h): the f32
 // instantiations of utt_fused_kernel and the entry points
-// mmb_mm2_stream_project and mmb_mm2_stream_project_ft.  The 16-bit
-// instantiations are in fused_f16_kernels.hip and fused_bf16_kernels.hip.
+// mmb_mm2_stream_project, mmb_mm2_stream_project_ft and
+// mmb_mm2_stream_project_tt.  The 16-bit instantiations are in
+// fused_f16_kernels.hip and fused_bf16_kernels.hip (frames) and in the six
+// fused_t<table>_<frames>_kernels.hip (a 16-bit word table).
 #include "mmb_fused.h"
 
 namespace mmb {
@@ -15,10 +17,22 @@ static int launch_fused(const FusedArgs& f, int grid, hipStream_t stream) {
   return MMB_OK;
 }
 
-// mmb_mm2_stream_project for frames of storage type frame_type
-// (MMB_FRAMES_*, validated by the caller): the checks, the launch geometry
-// and the column bounds are the same for the three.
-static int fused_project(int frame_type, const int32_t* ids, const float* table, int64_t v,
+// the launch for a word table of storage type table_type and frames of
+// storage type frame_type: each pair's kernels live in a source of their own
+static int launch_fused_pair(int table_type, int frame_type, const FusedArgs& f, int grid, hipStream_t stream) {
+  using Launch = int (*)(const FusedArgs&, int, hipStream_t);
+  static constexpr Launch kLaunch[3][3] = {
+      {launch_fused, launch_fused_f16, launch_fused_bf16},
+      {launch_fused_tf16_f32, launch_fused_tf16_f16, launch_fused_tf16_bf16},
+      {launch_fused_tbf16_f32, launch_fused_tbf16_f16, launch_fused_tbf16_bf16}};
+  return kLaunch[table_type][frame_type](f, grid, stream);
+}
+
+// mmb_mm2_stream_project for a word table of storage type table_type
+// (MMB_TABLE_*) and frames of storage type frame_type (MMB_FRAMES_*), both
+// validated by the caller: the checks, the launch geometry and the column
+// bounds are the same for the nine pairs.
+static int fused_project(int table_type, int frame_type, const int32_t* ids, const void* table, int64_t v,
                          const float* wtab32, const float* text_dense, const float* w_dense,
                          const void* audio, const void* visual, int64_t n, int t, int d, int a_, int vd,
                          const void* wpieces, const float* c0, float* num_out, float* aux_out,
@@ -27,13 +41,14 @@ static int fused_project(int frame_type, const int32_t* ids, const float* table,
   FusedArgs f{};
   // the weighted sum's rows are the text frames themselves; the sums stay on
   // chip (no s_out), fp16 hi | lo
-  if (const int rc = stream_args(&f.s, ids, table, v, wtab32, text_dense, text_dense, w_dense, audio, visual, n, t,
+  if (const int rc = stream_args(&f.s, ids, static_cast<const float*>(table), v, wtab32, text_dense, text_dense, w_dense, audio, visual, n, t,
                                  d, a_, vd, num_out, nullptr, 1, aux_out, flag, colmax, colmax_ws))
     return rc;
   MMB_REQUIRE(mmb_mm2_stream_project_supported(t, d, a_, vd) && mmb2_out && wpieces && c0);
   // vector rows are required here, not an option: no scalar fused kernel
-  // (stream_vec's width % 4 asks nothing new: the predicate above has it)
-  const StreamVec vec = stream_vec(f.s, frame_bytes(frame_type));
+  // (stream_vec's width % 4 asks nothing new: the predicate above has it);
+  // a unit of 4 values is one load: 16 bytes of f32, 8 of a 16-bit type
+  const StreamVec vec = stream_vec(f.s, frame_bytes(frame_type), table_bytes(table_type));
   MMB_REQUIRE(vec.t && vec.a && vec.v && aligned16(num_out) && aligned16(wpieces));
   if (n == 0) return empty_call(colmax, d, stream);
   f.kq[0] = piece_k(d);
@@ -67,9 +82,7 @@ static int fused_project(int frame_type, const int32_t* ids, const float* table,
     f.nu = f.big + ceil_div(n - f.big * kGR, kGR / 4);
     if (const int rc = zero_words_async(f.sched, 1, stream)) return rc;
   }
-  const int rc = frame_type == MMB_FRAMES_F32   ? launch_fused(f, grid, stream)
-                 : frame_type == MMB_FRAMES_F16 ? launch_fused_f16(f, grid, stream)
-                                                : launch_fused_bf16(f, grid, stream);
+  const int rc = launch_fused_pair(table_type, frame_type, f, grid, stream);
   // the bounds: a partial row per streamer wave
   return reduce_colmax(rc, f.s, grid * 4, colmax, stream);
 }
@@ -92,7 +105,7 @@ extern "C" int mmb_mm2_stream_project(const int32_t* ids, const float* table, in
                                       const float* c0, float* num_out, float* aux_out,
                                       float* mmb2_out, int32_t* flag, uint32_t* colmax,
                                       void* colmax_ws, hipStream_t stream) {
-  return fused_project(MMB_FRAMES_F32, ids, table, v, wtab32, text_dense, w_dense, audio, visual, n, t, d, a_, vd,
+  return fused_project(MMB_TABLE_F32, MMB_FRAMES_F32, ids, table, v, wtab32, text_dense, w_dense, audio, visual, n, t, d, a_, vd,
                        wpieces, c0, num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
 }
 
@@ -104,8 +117,20 @@ extern "C" int mmb_mm2_stream_project_ft(const int32_t* ids, const float* table,
                                          uint32_t* colmax, void* colmax_ws, hipStream_t stream) {
   MMB_REQUIRE(frame_bytes(frame_type) != 0);
   MMB_REQUIRE(ids);  // gathered text only
-  return fused_project(frame_type, ids, table, v, wtab32, nullptr, w_dense, audio, visual, n, t, d, a_, vd, wpieces,
-                       c0, num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
+  return fused_project(MMB_TABLE_F32, frame_type, ids, table, v, wtab32, nullptr, w_dense, audio, visual, n, t, d, a_,
+                       vd, wpieces, c0, num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
+}
+
+extern "C" int mmb_mm2_stream_project_tt(const int32_t* ids, const void* table, int table_type, int64_t v,
+                                         const float* wtab32, const float* w_dense, const void* audio,
+                                         const void* visual, int frame_type, int64_t n, int t, int d,
+                                         int a_, int vd, const void* wpieces, const float* c0,
+                                         float* num_out, float* aux_out, float* mmb2_out, int32_t* flag,
+                                         uint32_t* colmax, void* colmax_ws, hipStream_t stream) {
+  MMB_REQUIRE(table_bytes(table_type) != 0 && frame_bytes(frame_type) != 0);
+  MMB_REQUIRE(ids);  // gathered text only
+  return fused_project(table_type, frame_type, ids, table, v, wtab32, nullptr, w_dense, audio, visual, n, t, d, a_,
+                       vd, wpieces, c0, num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
 }
 
 // the tools build's variant launches, knobs and probes (tools/diag/); the

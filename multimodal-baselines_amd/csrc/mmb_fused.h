@@ -1,9 +1,11 @@
 // The MMB2 stream and its projection in one kernel: utt_fused_kernel and its
-// launchers, shared by the sources that instantiate it -- one per frame
-// element type (fused_kernels.hip: f32 frames, the entry points and the tools
-// tail; fused_f16_kernels.hip, fused_bf16_kernels.hip: 16-bit frames), so
-// that no translation unit compiles more fused kernels than the f32 one.
-// The template is instantiated for a given FE in exactly one of them.
+// launchers, shared by the sources that instantiate it -- one per pair of
+// frame and word-table element types (fused_kernels.hip: f32 frames on an f32
+// table, the entry points and the tools tail; fused_f16_kernels.hip,
+// fused_bf16_kernels.hip: 16-bit frames on an f32 table; the six
+// fused_t<table>_<frames>_kernels.hip: a 16-bit table), so that no
+// translation unit compiles more fused kernels than the f32 one.  The
+// template is instantiated for a given (FE, TE) in exactly one of them.
 #pragma once
 #include "mmb_stream.h"
 
@@ -111,77 +113,8 @@ __device__ __forceinline__ void fused_signal_lds(int* p) {
     __hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// Text piece of utterance i (one wave, lane l owns float4 columns l, l + 64):
-// the weighted sum num = sum_t w_t E_t, Sx, Sxx of the gathered rows, the
-// count of nonzero weights and their sum (utt_sums' text half).
-template <int UNR>
-__device__ __forceinline__ void text_piece(const StreamArgs& a, int64_t i, int lane, float4 (&num)[2],
-                                           float4 (&sx)[2], float4 (&sxx)[2], float& cnt, float& sw) {
-  const int UT = a.D >> 2;
-  const float* tsrc = a.ids ? a.table : a.text_dense;
-  const bool gather = a.ids != nullptr;
-  int rid = -1;
-  float w = 0.f;
-  if (lane < a.L) {
-    int64_t off;
-    stage_token(a, i, lane, off, w);
-    rid = off < 0 ? -1 : (gather ? static_cast<int>(off / a.D) : lane);
-  }
-  cnt = wave_sum((w != 0.f) ? 1.f : 0.f);
-  sw = wave_sum_dpp_f32(w);  // DPP rows, as the pipelined streamers (bit-identical variants)
-  if (lane == 0 && cnt == 0.f && a.flag) atomicOr(a.flag, MMB_FLAG_ZERO_WEIGHTS);
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int c = 0; c < 2; ++c) num[c] = sx[c] = sxx[c] = z4;
-  const int64_t dbase = i * a.L;
-  const int ct0 = 4 * min(lane, UT - 1), ct1 = 4 * min(lane + kWave, UT - 1);
-  auto frame = [&](int t, float4 (&v)[2], float& wt, bool& ok) {
-    const int r = __builtin_amdgcn_readlane(rid, t);
-    wt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), t));
-    ok = r >= 0;
-    const int64_t o = (gather ? static_cast<int64_t>(ok ? r : 0) : dbase + t) * a.D;
-    v[0] = ld4(tsrc + o + ct0);
-    v[1] = ld4(tsrc + o + ct1);
-  };
-  auto accum = [&](const float4 (&v)[2], float wt, bool ok) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const float4 x = ok ? v[c] : z4;
-      fma4(num[c], wt, x);
-      add4(sx[c], x);
-      sq4(sxx[c], x);
-    }
-  };
-  int t = 0;
-  for (; t + UNR <= a.L; t += UNR) {
-    float4 v[UNR][2];
-    float wt[UNR];
-    bool ok[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) frame(t + u, v[u], wt[u], ok[u]);
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) accum(v[u], wt[u], ok[u]);
-  }
-  for (; t + 4 <= a.L; t += 4) {  // tail groups: keep loads in flight
-    float4 v[4][2];
-    float wt[4];
-    bool ok[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) frame(t + u, v[u], wt[u], ok[u]);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) accum(v[u], wt[u], ok[u]);
-  }
-  for (; t < a.L; ++t) {
-    float4 v[2];
-    float wt;
-    bool ok;
-    frame(t, v, wt, ok);
-    accum(v, wt, ok);
-  }
-}
-
-// A frame column unit (4 values) as it is loaded: a float4, or on 16-bit
-// frames the 8-byte unit, kept packed until the frame is summed.
+// A column unit (4 values) of a frame or a word-table row as it is loaded: a
+// float4, or of a 16-bit type the 8-byte unit, kept packed until it is summed.
 template <class FE>
 using frame_unit = std::conditional_t<std::is_same_v<FE, float>, float4, u2>;
 template <bool NT, class FE>
@@ -200,6 +133,82 @@ __device__ __forceinline__ float4 unit_f32x4(const frame_unit<FE>& q) {
     return q;
   } else {
     return frame_f32x4<FE>(q);
+  }
+}
+
+// Text piece of utterance i (one wave, lane l owns float4 columns l, l + 64):
+// the weighted sum num = sum_t w_t E_t, Sx, Sxx of the gathered rows, the
+// count of nonzero weights and their sum (utt_sums' text half).  TE: the word
+// table's element type; a 16-bit row unit is one 8-byte load, kept packed
+// until it is summed (gathered text only: dense text is f32).
+template <int UNR, class TE = float>
+__device__ __forceinline__ void text_piece(const StreamArgs& a, int64_t i, int lane, float4 (&num)[2],
+                                           float4 (&sx)[2], float4 (&sxx)[2], float& cnt, float& sw) {
+  const int UT = a.D >> 2;
+  const TE* tsrc = frames<TE>(a.ids ? a.table : a.text_dense);
+  const bool gather = a.ids != nullptr;
+  int rid = -1;
+  float w = 0.f;
+  if (lane < a.L) {
+    int64_t off;
+    stage_token(a, i, lane, off, w);
+    rid = off < 0 ? -1 : (gather ? static_cast<int>(off / a.D) : lane);
+  }
+  cnt = wave_sum((w != 0.f) ? 1.f : 0.f);
+  sw = wave_sum_dpp_f32(w);  // DPP rows, as the pipelined streamers (bit-identical variants)
+  if (lane == 0 && cnt == 0.f && a.flag) atomicOr(a.flag, MMB_FLAG_ZERO_WEIGHTS);
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int c = 0; c < 2; ++c) num[c] = sx[c] = sxx[c] = z4;
+  const int64_t dbase = i * a.L;
+  const int ct0 = 4 * min(lane, UT - 1), ct1 = 4 * min(lane + kWave, UT - 1);
+  auto frame = [&](int t, frame_unit<TE> (&v)[2], float& wt, bool& ok) {
+    const int r = __builtin_amdgcn_readlane(rid, t);
+    wt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), t));
+    ok = r >= 0;
+    const int64_t o = (gather ? static_cast<int64_t>(ok ? r : 0) : dbase + t) * a.D;
+    v[0] = ld_unit<false>(tsrc + o + ct0);
+    v[1] = ld_unit<false>(tsrc + o + ct1);
+  };
+  auto accum = [&](const frame_unit<TE> (&v)[2], float wt, bool ok) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      float4 x;
+      if constexpr (std::is_same_v<TE, float>) {
+        x = ok ? v[c] : z4;
+      } else {  // (a 16-bit row unit: widened here)
+        x = ok ? unit_f32x4<TE>(v[c]) : z4;
+      }
+      fma4(num[c], wt, x);
+      add4(sx[c], x);
+      sq4(sxx[c], x);
+    }
+  };
+  int t = 0;
+  for (; t + UNR <= a.L; t += UNR) {
+    frame_unit<TE> v[UNR][2];
+    float wt[UNR];
+    bool ok[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) frame(t + u, v[u], wt[u], ok[u]);
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) accum(v[u], wt[u], ok[u]);
+  }
+  for (; t + 4 <= a.L; t += 4) {  // tail groups: keep loads in flight
+    frame_unit<TE> v[4][2];
+    float wt[4];
+    bool ok[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) frame(t + u, v[u], wt[u], ok[u]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) accum(v[u], wt[u], ok[u]);
+  }
+  for (; t < a.L; ++t) {
+    frame_unit<TE> v[2];
+    float wt;
+    bool ok;
+    frame(t, v, wt, ok);
+    accum(v, wt, ok);
   }
 }
 
@@ -258,24 +267,26 @@ __device__ __forceinline__ void frame_piece(const FE* base, int W, int L, int la
 // The pipelined streamers' frame loads (one frame of a group in flight; the
 // group's storage is a float4 and a float per frame whatever the piece, since
 // a piece's tail prefetches the next piece's first group into it):
-//   text rows and f32 frames   one b128 load (lane l: columns 4 l .. 4 l + 3)
-//                              and, TAIL, one b32 load of column 256 + l
-//   16-bit frames              one b64 load of the same four columns, held
-//                              packed in va.x | va.y, and, TAIL, one b16 load
+//   f32 rows (text of an f32   one b128 load (lane l: columns 4 l .. 4 l + 3)
+//   table or dense, frames)    and, TAIL, one b32 load of column 256 + l
+//   16-bit rows (text of a     one b64 load of the same four columns, held
+//   16-bit table, frames)      packed in va.x | va.y, and, TAIL, one b16 load
 //                              held zero-extended in vb
 // o0 / o1 are the lane's byte offsets of the two loads, so the frame's (a
 // scalar).  Both loads clamp their column to the row's last, share the
 // descriptor, the scalar row offset and the cache policy; the loads per frame
-// are the same for every FE, and with them the counted vmcnt waits.
-template <class FE, bool TEXT>
-constexpr int kFrameBytes = (TEXT || std::is_same_v<FE, float>) ? 4 : 2;
+// are the same for every FE and TE, and with them the counted vmcnt waits.
+// (The text of a 16-bit table TE is gathered: dense text is f32, and the
+// entry point hands a TE kernel ids.)
+template <class FE, bool TEXT, class TE = float>
+constexpr int kFrameBytes = std::is_same_v<std::conditional_t<TEXT, TE, FE>, float> ? 4 : 2;
 // an element of that many bytes: what a row's buffer descriptor is based on
 // (a typed row pointer, not bytes: the f32 instantiations keep their code)
 template <int BYTES>
 using frame_row_t = std::conditional_t<BYTES == 4, float, uint16_t>;
-template <class FE, bool TEXT, bool TAIL, int POL, class R>
+template <class FE, bool TEXT, bool TAIL, int POL, class TE = float, class R>
 __device__ __forceinline__ void load_frame(R rsrc, int o0, int o1, int so, float4& va, float& vb) {
-  if constexpr (kFrameBytes<FE, TEXT> == 4) {
+  if constexpr (kFrameBytes<FE, TEXT, TE> == 4) {
     va = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o0, so, POL));
     if constexpr (TAIL) vb = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, o1, so, POL));
   } else {
@@ -287,7 +298,7 @@ __device__ __forceinline__ void load_frame(R rsrc, int o0, int o1, int so, float
           __builtin_bit_cast(uint16_t, __builtin_amdgcn_raw_buffer_load_b16(rsrc, o1, so, POL))));
   }
 }
-// what load_frame left of an audio / visual frame, widened (exactly) to f32
+// what load_frame left of a frame (FE) or a table row (TE), widened (exactly) to f32
 template <class FE>
 __device__ __forceinline__ float4 group_f32x4(const float4& va) {
   if constexpr (std::is_same_v<FE, float>) {
@@ -327,7 +338,12 @@ __device__ __forceinline__ float group_f32(float vb) {
 // are widened exactly where a frame is summed, and the sums' statements are
 // the f32 instantiation's in their order: a launch on 16-bit frames writes,
 // bit for bit, what the same launch writes on those frames upcast to f32.
-template <int UNR, bool NT, int DIAG = 0, int PIPE = 0, int SL = kGSlots, int TM = 7, class FE = float>
+// TE: the element type of the word table (a.table is then read through
+// const TE*; gathered text only).  A 16-bit row travels as the 16-bit frames
+// do -- the same two loads, packed until summed, the exact widening -- so the
+// same equality holds for the table upcast to f32, for each FE.
+template <int UNR, bool NT, int DIAG = 0, int PIPE = 0, int SL = kGSlots, int TM = 7, class FE = float,
+          class TE = float>
 __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void utt_fused_kernel(
     FusedArgs f) {
   const StreamArgs& a = f.s;
@@ -531,7 +547,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
               num[0] = num[1] = sx[0] = sx[1] = sxx[0] = sxx[1] = o4;
               cnt = sw = 1.f;
             } else if (m == 0) {
-              text_piece<UNR>(a, i, lane, num, sx, sxx, cnt, sw);
+              text_piece<UNR, TE>(a, i, lane, num, sx, sxx, cnt, sw);
             } else {
               const FE* base = m == 1 ? frames<FE>(a.audio) + i * a.L * a.A : frames<FE>(a.visual) + i * a.L * a.Vd;
               frame_piece<UNR, NT, FE>(base, W, a.L, lane, sx, sxx);
@@ -556,7 +572,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
       // (A pipeline running on across piece and batch boundaries, one issue /
       // consume pair for all three modalities, measured 29.4 vs 22.1 ms: the
       // shared register sets made the compiler drain every group, vmcnt(0).)
-      const bool gather = a.ids != nullptr;
+      const bool gather = a.ids != nullptr;  // (always, of a 16-bit table: dense text is f32)
       const int L = a.L;
       // the wave index made visibly wave-uniform (SGPR): rows, loop bounds and
       // buffer descriptors derive from it (a descriptor in VGPRs would be
@@ -632,7 +648,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
         // issued on its 11 live lanes only, the others zeroed, measured 23.37
         // vs 22.24 ms: the divergent branch costs more than the clamped
         // duplicate addresses, which the L1 coalesces.)
-        constexpr int EB = kFrameBytes<FE, TEXT>;  // bytes per element of this piece's rows
+        constexpr int EB = kFrameBytes<FE, TEXT, TE>;  // bytes per element of this piece's rows
         using RowE = frame_row_t<EB>;
         const int vo0 = 4 * EB * min(lane, UW - 1), vo1 = EB * min(4 * kWave + lane, W - 1);
         auto issue = [&](int g, Grp& v) {
@@ -641,22 +657,22 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
           int rid = 0;
           if constexpr (TEXT) rid = rr == cur ? rid_c : rid_n;
           const bool rowbase = !TEXT || !gather;  // frames [L][W] of row i
-          const RowE* rsrc_base = frames<RowE>(src);  // (text: never 16-bit)
+          const RowE* rsrc_base = frames<RowE>(src);
           const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(
               const_cast<RowE*>(rowbase ? rsrc_base + i * L * W : rsrc_base), 0,
-              rowbase ? L * W * EB : static_cast<int>(a.V * D * 4), 0x00020000);
+              rowbase ? L * W * EB : static_cast<int>(a.V * D * EB), 0x00020000);
 #pragma unroll
           for (int u = 0; u < UNR; ++u) {
             const int t = min(t0 + u, L - 1);
             int so;
             if constexpr (TEXT) {
               const int r = __builtin_amdgcn_readlane(rid, t);
-              so = gather ? (r >= 0 ? r : 0) * D * 4 : t * W * 4;
+              so = gather ? (r >= 0 ? r : 0) * D * EB : t * W * EB;
             } else {
               so = t * W * EB;
             }
             constexpr int pol = (!TEXT && NT) ? 2 : 0;  // non-temporal frame streams
-            load_frame<FE, TEXT, TAIL, pol>(rsrc, vo0, vo1, so, v.a[u], v.b[u]);
+            load_frame<FE, TEXT, TAIL, pol, TE>(rsrc, vo0, vo1, so, v.a[u], v.b[u]);
           }
         };
         auto sum_frame = [&](int t, const float4& va, float vb) {
@@ -664,12 +680,22 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
             const int r = __builtin_amdgcn_readlane(rid_c, t);
             const float wt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w_c), t));
             const bool ok = r >= 0;  // an out-of-range id (flagged) contributes a zero row
-            const float4 x = ok ? va : z4;
+            float4 x;
+            if constexpr (std::is_same_v<TE, float>) {
+              x = ok ? va : z4;
+            } else {  // (a 16-bit row: the packed unit widened here)
+              x = ok ? group_f32x4<TE>(va) : z4;
+            }
             fma4(num, wt, x);
             add4(sx, x);
             sq4(sxx, x);
             if constexpr (TAIL) {
-              const float xt = ok ? vb : 0.f;
+              float xt;
+              if constexpr (std::is_same_v<TE, float>) {
+                xt = ok ? vb : 0.f;
+              } else {
+                xt = ok ? group_f32<TE>(vb) : 0.f;
+              }
               numt = fmaf(wt, xt, numt);
               sxt += xt;
               sxxt = fmaf(xt, xt, sxxt);
@@ -785,7 +811,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
             tok_resolve(raw, wd, rid_c, w_c);
           }
         }
-        constexpr int EB = kFrameBytes<FE, TEXT>;  // bytes per element of this piece's rows
+        constexpr int EB = kFrameBytes<FE, TEXT, TE>;  // bytes per element of this piece's rows
         const int vo0 = 4 * EB * min(lane, UW - 1), vo1 = EB * min(4 * kWave + lane, W - 1);
         // group g of this piece (or, NX, group 0 of the next piece) into v
         auto load_group = [&](auto nx_c, int g, Grp& v) {
@@ -793,7 +819,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
           constexpr int MM = NX ? (M + 1) % 3 : M;
           constexpr bool T2 = MM == 0;
           constexpr bool TAIL2 = ((TM >> MM) & 1) != 0;
-          constexpr int E2 = kFrameBytes<FE, T2>;
+          constexpr int E2 = kFrameBytes<FE, T2, TE>;
           const int rr = NX ? 0 : g / ngr, t0 = NX ? 0 : (g - rr * ngr) * UNR;
           const int64_t i = NX ? (M == 2 ? ni0 : i0) : i0 + 4 * rr;
           const int W2 = wdt[MM], U2 = W2 >> 2;
@@ -803,22 +829,22 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
           if constexpr (T2) rid = NX ? rid_pre : (rr == cur ? rid_c : rid_n);
           const bool rowbase = !T2 || !gather;
           using Row2 = frame_row_t<E2>;
-          const Row2* r2 = frames<Row2>(s2);  // (text: never 16-bit)
+          const Row2* r2 = frames<Row2>(s2);
           const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(
               const_cast<Row2*>(rowbase ? r2 + i * L * W2 : r2), 0,
-              rowbase ? L * W2 * E2 : static_cast<int>(a.V * D * 4), 0x00020000);
+              rowbase ? L * W2 * E2 : static_cast<int>(a.V * D * E2), 0x00020000);
 #pragma unroll
           for (int u = 0; u < UNR; ++u) {
             const int t = min(t0 + u, L - 1);
             int so;
             if constexpr (T2) {
               const int r = __builtin_amdgcn_readlane(rid, t);
-              so = gather ? (r >= 0 ? r : 0) * D * 4 : t * W2 * 4;
+              so = gather ? (r >= 0 ? r : 0) * D * E2 : t * W2 * E2;
             } else {
               so = t * W2 * E2;
             }
             constexpr int pol = (!T2 && NT) ? 2 : 0;  // non-temporal frame streams
-            load_frame<FE, T2, TAIL2, pol>(rsrc, o0, o1, so, v.a[u], v.b[u]);
+            load_frame<FE, T2, TAIL2, pol, TE>(rsrc, o0, o1, so, v.a[u], v.b[u]);
           }
         };
         auto issue = [&](int g, Grp& v) { load_group(std::false_type{}, g, v); };
@@ -827,12 +853,22 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
             const int r = __builtin_amdgcn_readlane(rid_c, t);
             const float wt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w_c), t));
             const bool ok = r >= 0;  // an out-of-range id (flagged) contributes a zero row
-            const float4 x = ok ? va : z4;
+            float4 x;
+            if constexpr (std::is_same_v<TE, float>) {
+              x = ok ? va : z4;
+            } else {  // (a 16-bit row: the packed unit widened here)
+              x = ok ? group_f32x4<TE>(va) : z4;
+            }
             fma4(num, wt, x);
             add4(sx, x);
             sq4(sxx, x);
             if constexpr (TAIL) {
-              const float xt = ok ? vb : 0.f;
+              float xt;
+              if constexpr (std::is_same_v<TE, float>) {
+                xt = ok ? vb : 0.f;
+              } else {
+                xt = ok ? group_f32<TE>(vb) : 0.f;
+              }
               numt = fmaf(wt, xt, numt);
               sxt += xt;
               sxxt = fmaf(xt, xt, sxxt);
@@ -1216,21 +1252,21 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
 }
 
 
-template <int DIAG, int UNR = 8, int PIPE = 0, int SL = kGSlots, int TM = 7, class FE = float>
+template <int DIAG, int UNR = 8, int PIPE = 0, int SL = kGSlots, int TM = 7, class FE = float, class TE = float>
 static void launch_fused_v(const FusedArgs& f, int grid, hipStream_t stream) {
   constexpr size_t lds = fused_lds_bytes(SL);
-  allow_dynamic_lds<&utt_fused_kernel<UNR, true, DIAG, PIPE, SL, TM, FE>>(lds);
-  utt_fused_kernel<UNR, true, DIAG, PIPE, SL, TM, FE><<<grid, kFThreads, lds, stream>>>(f);
+  allow_dynamic_lds<&utt_fused_kernel<UNR, true, DIAG, PIPE, SL, TM, FE, TE>>(lds);
+  utt_fused_kernel<UNR, true, DIAG, PIPE, SL, TM, FE, TE><<<grid, kFThreads, lds, stream>>>(f);
 }
 // the pipelined streamer specialised for the pieces that carry a row tail
 // (a piece-level, wave-uniform choice made here, once per launch)
 // (the mask TM: bit 0 text, bit 1 audio, bit 2 visual; asked as "no tail",
 // visual first, so that the kernels are instantiated in the order TM = 0..7)
-template <int UNR, int PIPE, class FE = float>
+template <int UNR, int PIPE, class FE = float, class TE = float>
 static void launch_fused_tm(const FusedArgs& f, int grid, hipStream_t stream) {
   dispatch3(f.s.Vd <= 4 * kWave, f.s.A <= 4 * kWave, f.s.D <= 4 * kWave, [&](auto v, auto a, auto t) {
     constexpr int TM = (t.value ? 0 : 1) | (a.value ? 0 : 2) | (v.value ? 0 : 4);
-    launch_fused_v<0, UNR, PIPE, kGSlots, TM, FE>(f, grid, stream);
+    launch_fused_v<0, UNR, PIPE, kGSlots, TM, FE, TE>(f, grid, stream);
   });
 }
 // the pipelined streamer's frames per load group (two groups in flight per
@@ -1239,7 +1275,8 @@ static void launch_fused_tm(const FusedArgs& f, int grid, hipStream_t stream) {
 // 20.9, 12 frames 22.0 (its last group of a row is one third live); the
 // parent's float4 tails with 8 frames 22.1.  The other
 // candidates live in the tools build (MMB_FUSED_UNR).  The 16-bit
-// instantiations keep the group size and depth (60 VGPRs of buffers).
+// instantiations keep the group size and depth (60 VGPRs of buffers), for
+// the frames and for the rows of a 16-bit table alike.
 constexpr int kFUnr = 10;
 // streamer: 1 = pipelined (two groups in flight: kernel 23.35 -> 22.49 ms,
 // step 25.14 -> 24.41 ms in a same-process A/B, r02k); 2 (default) = also
@@ -1247,37 +1284,48 @@ constexpr int kFUnr = 10;
 // 0 = one group at a time, 8 frames each, float4 row tails (the fallback for
 // rows of < 3 frame groups or a word table >= 2 GB, and the bit-identical
 // reference of the tests)
+template <class TE = float>
 static bool fused_pipe_ok(const FusedArgs& f, int un) {
   // the pipelined streamer stages a text row's tokens two groups before its
   // first group is issued (ids at the row before's first group, wtab[id] at
   // its second): >= 3 groups of un frames per row -- T >= 21 at the product's
   // 10-frame groups, shorter rows take the fallback; it addresses the word
-  // table through one buffer descriptor (< 2^31 bytes)
-  return (f.s.L + un - 1) / un >= 3 && (f.s.ids == nullptr || f.s.V * f.s.D * 4 < (int64_t{1} << 31));
+  // table through one buffer descriptor (< 2^31 bytes: a 16-bit table keeps
+  // it up to twice the rows)
+  return (f.s.L + un - 1) / un >= 3 &&
+         (f.s.ids == nullptr || f.s.V * f.s.D * static_cast<int>(sizeof(TE)) < (int64_t{1} << 31));
 }
 
 static int fused_grid(int64_t nb, hipStream_t stream) {
   return static_cast<int>(std::min<int64_t>(nb, std::min(stream_cu_count(stream), kCmaxRows / 4)));
 }
 
-// the product's two kernels for frames of type FE: the pipelined streamer
-// per tail mask, or the group-at-a-time fallback
-template <class FE>
+// the product's two kernels for frames of type FE and a word table of type
+// TE: the pipelined streamer per tail mask, or the group-at-a-time fallback
+template <class FE, class TE = float>
 static int launch_fused_frames(const FusedArgs& f, int grid, hipStream_t stream) {
-  if (fused_pipe_ok(f, kFUnr)) {
-    launch_fused_tm<kFUnr, 2, FE>(f, grid, stream);
+  if (fused_pipe_ok<TE>(f, kFUnr)) {
+    launch_fused_tm<kFUnr, 2, FE, TE>(f, grid, stream);
   } else {
-    launch_fused_v<0, 8, 0, kGSlots, 7, FE>(f, grid, stream);
+    launch_fused_v<0, 8, 0, kGSlots, 7, FE, TE>(f, grid, stream);
   }
   MMB_LAUNCH_CHECK();
   return MMB_OK;
 }
 
-// the 16-bit instantiations' launches (fused_f16_kernels.hip,
-// fused_bf16_kernels.hip), called by mmb_mm2_stream_project_ft
+// the 16-bit instantiations' launches, one source each: 16-bit frames on an
+// f32 table (fused_f16_kernels.hip, fused_bf16_kernels.hip), called by
+// mmb_mm2_stream_project_ft, and a 16-bit table under each frame type
+// (fused_t<table>_<frames>_kernels.hip), called by mmb_mm2_stream_project_tt
 #pragma GCC visibility push(hidden)
 int launch_fused_f16(const FusedArgs& f, int grid, hipStream_t stream);
 int launch_fused_bf16(const FusedArgs& f, int grid, hipStream_t stream);
+int launch_fused_tf16_f32(const FusedArgs& f, int grid, hipStream_t stream);
+int launch_fused_tf16_f16(const FusedArgs& f, int grid, hipStream_t stream);
+int launch_fused_tf16_bf16(const FusedArgs& f, int grid, hipStream_t stream);
+int launch_fused_tbf16_f32(const FusedArgs& f, int grid, hipStream_t stream);
+int launch_fused_tbf16_f16(const FusedArgs& f, int grid, hipStream_t stream);
+int launch_fused_tbf16_bf16(const FusedArgs& f, int grid, hipStream_t stream);
 #pragma GCC visibility pop
 
 }  // namespace mmb

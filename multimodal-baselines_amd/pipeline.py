@@ -101,8 +101,9 @@ def seq2weight(seq32: torch.Tensor, sel: torch.Tensor | None, wtab64: torch.Tens
 
 # Storage types of the word table: the name step_plan and FusedStep use ->
 # (torch dtype, the table_type of mmb_sif_wavg_tt / mmb_mm2_stream_tt).  The
-# 16-bit kinds are read by the SIF gather and the plain stream kernels only
-# (weighted_sum, sif_embeddings, mm2_stream); nothing here converts a table.
+# 16-bit kinds are read by the SIF gather, the plain stream kernels and the
+# fused stream + projection kernel (weighted_sum, sif_embeddings, mm2_stream,
+# mm2_stream_project_tt); nothing here converts a table.
 TABLE_KINDS = {"f32": (torch.float32, L.MMB_TABLE_F32),
                "f16": (torch.float16, L.MMB_TABLE_F16),
                "bf16": (torch.bfloat16, L.MMB_TABLE_BF16)}
@@ -760,6 +761,27 @@ def mm2_stream_project_ft(n, t, d, a, vd, audio, visual, proj: "MMB2Projection",
                            proj, ids32, table, wtab32, flag, out, colmax, colmax_ws)
 
 
+def mm2_stream_project_tt(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", ids32, table,
+                          wtab32, w_dense=None, flag=None, out=None, colmax=None, colmax_ws=None):
+    """mm2_stream_project_ft on a word table of any TABLE_KINDS dtype as well
+    (mmb_mm2_stream_project_tt; gathered text only, all nine pairs of table
+    and frame dtypes): `table` may be float16 or bfloat16, from an 8-byte
+    aligned base, and the outputs are bit for bit those of the same table
+    upcast to float32.  Returns (x, aux, mmb2)."""
+    who = "mm2_stream_project_tt"
+    kind = frame_kind(audio, visual, who)
+    if ids32 is None or table is None:
+        raise L.MMBError(f"{who}: gathered text (ids32 + table) only; dense text is float32 and reads no table")
+    tkind = table_kind(table, who)
+    proj.enable_pieces()
+    num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
+    L.call("mmb_" + who, L.ptr(ids32), L.ptr(table), TABLE_KINDS[tkind][1], table.shape[0], L.ptr(wtab32),
+           L.ptr(w_dense), L.ptr(audio), L.ptr(visual), FRAME_KINDS[kind][1], n, t, d, a, vd,
+           L.ptr(proj.wpieces), L.ptr(proj.c0), L.ptr(num), L.ptr(aux), L.ptr(mmb2), L.ptr(flag),
+           L.ptr(colmax), L.ptr(colmax_ws), L.stream_ptr())
+    return num, aux, mmb2
+
+
 def _fused_outputs(n: int, d: int, device, out, colmax_ws):
     """(x, aux, mmb2) of the fused wrappers -- `out` if given, else allocated
     -- after the workspace's size check."""
@@ -925,7 +947,8 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
               fork_projection: bool | None = None, split_stream: bool | None = None,
               split_projection: bool = True, frames: str = "f32",
               fused_frames16: bool = False, narrow_frames16: bool = False,
-              split_frames16: bool = False, table: str = "f32") -> StepPlan:
+              split_frames16: bool = False, fused_table16: bool = False,
+              table: str = "f32") -> StepPlan:
     """The plan of a step over `n` of a split's `n_total` utterances on a chip
     of `cus` CUs; the remaining arguments are FusedStep's overrides (None: by
     shape).  Precedence: the fused front kernels need one chunk ASKED for and
@@ -949,16 +972,24 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
     A 16-bit word `table` ("f16" / "bf16", TABLE_KINDS) is read by the plain
     stream kernel only: `stream_project`, `narrow_fused` and `split_stream`
     are off whatever the overrides and the three `*_frames16` opt-ins say, so
-    the plan is the two-kernel plan of the shape; with "f32" every plan is as
-    described above.  The table kind is not a field of the plan."""
+    the plan is the two-kernel plan of the shape -- unless `fused_table16`
+    opts in to the wide-frame fused kernel on it (mmb_mm2_stream_project_tt):
+    `stream_project` then keeps the caller's value and the front is "fused"
+    exactly where the f32-table plan of the same shape and frames chooses it
+    (on 16-bit frames that still needs `fused_frames16`); `narrow_fused` and
+    `split_stream` stay off.  With "f32" the keyword changes nothing and every
+    plan is as described above.  The table kind is not a field of the plan."""
     check_npc(npc)
     if frames not in FRAME_KINDS:
         raise ValueError(f"frames must be one of {', '.join(FRAME_KINDS)}, not {frames!r}")
     if table not in TABLE_KINDS:
         raise ValueError(f"table must be one of {', '.join(TABLE_KINDS)}, not {table!r}")
     if table != "f32":
-        stream_project = narrow_fused = split_stream = False
-        fused_frames16 = narrow_frames16 = split_frames16 = False
+        narrow_fused = split_stream = False
+        narrow_frames16 = split_frames16 = False
+        if not fused_table16:
+            stream_project = False
+            fused_frames16 = False
     if frames != "f32":
         if not split_frames16:
             split_stream = False
@@ -1077,9 +1108,13 @@ class FusedStep:
     (mm2_stream_split_ft; POM's long transcripts).
 
     A 16-bit word table (float16 / bfloat16 `inputs["table"]`, `self.table_kind`)
-    takes the two-kernel step whatever the overrides and opt-ins say
-    (mmb_mm2_stream_tt: the same rows bit for bit as on the upcast table), with
-    frames of any of the three dtypes.
+    takes the two-kernel step (mmb_mm2_stream_tt: the same rows bit for bit as
+    on the upcast table), with frames of any of the three dtypes;
+    `fused_table16=True` opts in to the fused stream + projection kernel on it
+    where the f32-table plan of the shape and frames would choose it
+    (mm2_stream_project_tt: no s buffer, the same rows bit for bit; on 16-bit
+    frames together with `fused_frames16`).  The narrow fused kernel and the
+    split stream read a float32 table only.
 
     Which of these a step takes is decided once, by step_plan() (`self.plan`);
     _run is one sequence over it: front kernel, chunk pipeline, projection
@@ -1094,7 +1129,8 @@ class FusedStep:
                  narrow_fused: bool | None = None, check_each_run: bool = False,
                  fork_projection: bool | None = None, split_stream: bool | None = None,
                  split_projection: bool = True, fused_frames16: bool = False,
-                 narrow_frames16: bool = False, split_frames16: bool = False):
+                 narrow_frames16: bool = False, split_frames16: bool = False,
+                 fused_table16: bool = False):
         self.inp = inputs
         self.check_each_run = check_each_run
         self.ids = inputs["ids"]
@@ -1112,6 +1148,7 @@ class FusedStep:
         # dtype its kernels would read as another
         self.frames = frame_kind(inputs["audio"], inputs["visual"], "FusedStep")
         # the word table's, likewise: a 16-bit table takes the two-kernel step
+        # (or, with fused_table16, the fused front's mm2_stream_project_tt)
         self.table_kind = table_kind(self.table, "FusedStep")
         self.plan = p = step_plan(self.n, self.n_total, self.t, self.d, self.a, self.vd, self.V, npc,
                                   L.cu_count(dev), chunks=chunks, fuse_remove=fuse_remove,
@@ -1120,7 +1157,7 @@ class FusedStep:
                                   split_stream=split_stream, split_projection=split_projection,
                                   frames=self.frames, fused_frames16=fused_frames16,
                                   narrow_frames16=narrow_frames16, split_frames16=split_frames16,
-                                  table=self.table_kind)
+                                  fused_table16=fused_table16, table=self.table_kind)
         self.proj = MMB2Projection(networks, self.d, self.a, self.vd, self.t, dev)
         kp = self.proj.kp
         self.x = torch.empty((self.n, self.d), dtype=torch.float32, device=dev)
@@ -1347,6 +1384,8 @@ class FusedStep:
             phase, front = _FRONTS[p.front]
             if p.frames != "f32":  # the fused kernels on 16-bit frames (fused_frames16 / narrow_frames16)
                 front = _FRONTS_FT[p.front]
+            if self.table_kind != "f32":  # the fused kernel on a 16-bit table (fused_table16), any frames
+                front = mm2_stream_project_tt
             with mark(phase):
                 front(self.n, self.t, self.d, self.a, self.vd, self.inp["audio"],
                       self.inp["visual"], self.proj, ids32=self.ids, table=self.table,
