@@ -23,6 +23,7 @@ import torch
 import mmb2_cases as C
 import mmb_lib
 from oracle import mmb2_oracle as M
+from plan_cases import _plan_cases
 
 KINDS = {"bf16": torch.bfloat16, "f16": torch.float16}
 
@@ -52,6 +53,24 @@ def check_arg_row(entry, args, base, change, want):
     else:
         with pytest.raises(mmb_lib.MMBError, match=r"code -1 \(invalid argument\)"):
             mmb_lib.call(entry, *call)
+
+
+# mmb_mm2_stream_ft's parameter names (the split `_ft` entry point's table builds on them)
+ARGS = ("ids table v wtab32 w_dense audio visual frame_type n t d a vd num_out s_out s_half aux_out "
+        "flag colmax colmax_ws stream").split()
+
+
+# ---------------------------------------------------------------- the plan
+def _shapes():
+    """The four real shapes of plan_cases' table, by name, for the 16-bit fronts' plan tests."""
+    by_name = {}
+    for shape, kw, want in _plan_cases():
+        key = (shape["n"], shape["t"], shape["a"], shape["vd"], shape["V"])
+        by_name.setdefault(key, shape)
+    want = {"c3": (1_000_000, 40, 300, 300, 400_000), "mosi": (1284, 20, 76, 48, 3016),
+            "pom": (100, 1089, 300, 300, 7763), "mid": (700, 40, 300, 300, 5000)}
+    return {name: by_name[key] for name, key in want.items()}
+
 
 # the steps test_gpu_frames16.py compares with the oracle: (D, A, Vd, T, N), V = DEFAULT_V
 STEP = [C.STEP[0], C.STEP[1], (300, 300, 300, 40, 97), (300, 76, 48, 20, 97), (50, 76, 48, 130, 16)]

@@ -1,59 +1,26 @@
-"""What the GPU tests of the 16-bit frame fronts share (tests/test_gpu_frames16.py,
-tests/test_gpu_fused_frames16.py, tests/test_gpu_narrow_frames16.py): device
-copies of a case's inputs, the buffers and the launch of a fused front, the
-launch on 16-bit frames beside its f32 twin and their bit-for-bit comparison,
-and the two-kernel step's twin inputs and oracle check.  Plain helper module:
-no test is collected from it.
+"""What the GPU tests of the 16-bit frame fronts and word tables share
+(tests/test_gpu_frames16.py, tests/test_gpu_fused_frames16.py,
+tests/test_gpu_narrow_frames16.py, tests/test_gpu_split_frames16.py,
+tests/test_gpu_table16.py, tests/test_gpu_fused_table16.py): the device copies
+of tests/common_gpu.py under their names, the buffers and the launch of a
+fused front, the launch on 16-bit frames beside its f32 twin and their
+bit-for-bit comparison, and the two-kernel step's twin inputs, twin keywords
+and oracle check.  Plain helper module: no test is collected from it.
 """
-import copy
-
 import numpy as np
 import torch
 
 import frames16_cases as F
 import mmb2_cases as C
-import mmb_lib as L
 import models
 import pipeline as P
 import synth
+from common_gpu import F32_ROW, TOL, _colmax_bufs, _dev, _i32, _networks, _off, _untouched  # noqa: F401  (passed on)
 from oracle import mmb2_oracle as M
 from oracle import sif_oracle as O
 
-TOL = 1e-5            # the end-to-end bar of the suite
-F32_ROW = 2.0 ** -23  # SIF rows: f32 rounding of the row's largest element, doubled
-
-
-def _dev(a, gpu, dtype=None):
-    t = a if isinstance(a, torch.Tensor) else torch.tensor(np.asarray(a))
-    return (t if dtype is None else t.to(dtype)).to(gpu)
-
-
-def _off(t, elements):
-    """A contiguous copy of `t` that starts `elements` elements past a 16-byte boundary."""
-    flat = torch.empty(t.numel() + elements, dtype=t.dtype, device=t.device)
-    out = flat[elements:].view(t.shape)
-    out.copy_(t)
-    assert out.is_contiguous() and out.data_ptr() % 16 == elements * t.element_size()
-    return out
-
-
-def _colmax_bufs(D, gpu):
-    nb = L.query("mmb_mm2_colmax_ws_bytes", D)
-    return (torch.zeros(D, dtype=torch.int32, device=gpu),
-            torch.empty((nb + 15) // 16 * 16, dtype=torch.uint8, device=gpu))
-
-
-def _networks(case, gpu):
-    return copy.deepcopy(C.generator(*case[:3])).to(gpu).networks()
-
-
-def _i32(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _untouched(out):
-    torch.cuda.synchronize()
-    return all(bool((t == -7.0).all()) for t in out)
+# the f32 twin of a step on 16-bit storage: the plain stream kernel + projection
+TWIN = dict(stream_project=False, narrow_fused=False, split_stream=False)
 
 
 # ------------------------------------------------------------------ the fused fronts
@@ -112,6 +79,14 @@ def _synth_case(D, A, Vd, T, N, V, kind, gpu):
 
 
 # ------------------------------------------------------------------ the step
+def _frames_of(case, kind, frames, gpu):
+    """The case's frames on the device: f32, or rounded to the table's kind."""
+    if frames == "f32":
+        z = C.inputs(case)
+        return _dev(z["audio"], gpu), _dev(z["visual"], gpu)
+    return tuple(_dev(t, gpu) for t in F.frames(case, kind))
+
+
 def _step_inputs(case, kind, gpu):
     """(the inputs with 16-bit frames, the same with their f32 upcast)."""
     z = C.inputs(case)

@@ -13,12 +13,12 @@ MMB2 rows, the column bounds and the flag word.
 from __future__ import annotations
 
 import frames16_cases as F
-import test_gpu_fused_tail as FT
+import fused_cases as FT
 from frames16_cases import BF16, EINVAL, F32, OK, P
 
 KINDS = F.KINDS
 
-# (D, A, Vd, T, N, bad ids): the shapes of tests/test_gpu_fused_tail.py, for its
+# (D, A, Vd, T, N, bad ids): the shapes of tests/fused_cases.py (tests/test_gpu_fused_tail.py), for its
 # reasons -- on 16-bit rows the b128 / b32 loads of a frame become a b64 and a
 # b16 load with their own lane offsets, clamps and descriptor ranges, so the
 # widths (no tail, 4 / 44 / 60 / 64 tail lanes, 1- and 5-lane pieces), the

@@ -13,16 +13,16 @@ types.
 from __future__ import annotations
 
 import frames16_cases as F
+import fused_cases as FT
 import fused_frames16_cases as FF
 import large_cases as LC
 import table16_cases as T
-import test_gpu_fused_tail as FT
 from frames16_cases import EINVAL, F32, OK, P
 from table16_cases import TABLE_TYPES, TABLE_TYPES16
 
 KINDS = T.KINDS
 
-# (D, A, Vd, T, N, bad ids): the shapes of tests/test_gpu_fused_tail.py, for its
+# (D, A, Vd, T, N, bad ids): the shapes of tests/fused_cases.py (tests/test_gpu_fused_tail.py), for its
 # reasons -- on a 16-bit table the b128 / b32 loads of a text row become a b64
 # and a b16 load with their own lane offsets, clamps, row offsets and
 # descriptor range, so the text widths (no tail, 4 / 44 / 60 tail lanes), the

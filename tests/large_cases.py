@@ -33,11 +33,12 @@ import collections
 
 import numpy as np
 
+from width_cases import F32_ROW  # noqa: F401  (the removals' f32 bar, for tests/test_large_cases.py)
+
 B31, B32 = 2 ** 31, 2 ** 32
 GIB = 2 ** 30
 MAX_CASE_BYTES = 16 * GIB
 MAX_SAMPLE = 64
-F32_ROW = 2.0 ** -23  # tests/test_gpu_widths.F32_ROW (imported there; restated for the CPU test only)
 
 
 class Operand(collections.namedtuple("Operand", "name rows row_bytes index")):

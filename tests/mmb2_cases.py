@@ -23,6 +23,7 @@ import synth
 from oracle import mmb2_oracle as M
 
 U = 2.0 ** -24  # unit roundoff of f32
+TOL = 1e-5      # the end-to-end bar of the suite: MMB2 and SIF rows against the oracle, row-relative
 
 # ---------------------------------------------------------------- the shape table: (D, A, Vd, T)
 # 1: wave stream kernel, D <= 256 (widths % 4, T <= 64): launch_wave<true, 1, CA, CV>

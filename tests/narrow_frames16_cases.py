@@ -83,7 +83,7 @@ SPECIAL_CASES = [(D, 76, 48, 20, 5, 3016), (D, 4, 4, 7, 5, 300)]
 
 # the step compared with its f32 narrow fused twin and the oracle: (D, A, Vd, T, N, V)
 STEP = (D, 76, 48, 20, 3000, 3016)
-# steps whose plan the keyword leaves alone, as (name in test_frames16_cases._shapes, why)
+# steps whose plan the keyword leaves alone, as (name in frames16_cases._shapes, why)
 PLAN_UNCHANGED = {"c3": "wide frames", "pom": "T > 64", "mid": "wide frames"}
 
 # ---------------------------------------------------------------- the argument table

@@ -1,7 +1,9 @@
 """Shared case tables, inputs and float64 references of
 tests/test_gpu_regressor_widths.py (GPU) and tests/test_regressor_cases.py
 (CPU): the sentiment regressor's kernels (csrc/mlp_kernels.hip) at widths
-other than 300.  Plain helper module: no test is collected from it.
+other than 300; tests/regressor_gpu.py, tests/test_gpu_scratch.py and
+tests/test_gpu_large.py read the same tables.  Plain helper module: no test
+is collected from it.
 
 Inputs are seeded from the case alone, rounded to f32 and widened back, so the
 device sees exactly what the float64 reference sees: rows N(0, 1), labels
@@ -18,6 +20,9 @@ from __future__ import annotations
 
 import collections
 import functools
+import importlib.util
+import json
+import os
 
 import numpy as np
 
@@ -27,6 +32,7 @@ MARGIN = 2.0
 N_EPOCHS = 2
 LR = float(np.float32(0.05))
 U32 = R.U32
+FLOOR = 8 * 2.0 ** -24  # the training bars (4x the float32 CPU run's own deviation) are not below this
 
 # LDS of mlp_train_mc_kernel (csrc/mlp_kernels.hip, train_lds_bytes): what
 # decides the largest width mmb_mlp_train accepts for a number of outputs
@@ -237,3 +243,30 @@ def backward_bounds(x, hid, w1, w2, dy):
         "dw2": (b + 1) * U32 * (np.abs(dy).T @ np.abs(hid)),
         "db2": (b + 1) * U32 * np.abs(dy).sum(0),
     }
+
+
+# ---------------------------------------------------------------- the recorded full-size runs
+# (tests/test_regressor_oracle.py on the CPU, tests/test_gpu_regressor.py on the device)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _gen():
+    spec = importlib.util.spec_from_file_location(
+        "make_goldens_regressor", os.path.join(GOLDEN, "make_goldens_regressor.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def full_case(name):
+    """(args, latents, labels, fixture, meta) of a g5_full* fixture, inputs
+    regenerated from the recorded seed and checked by checksum."""
+    g = _gen()
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    with open(os.path.join(GOLDEN, name + ".json")) as f:
+        meta = json.load(f)
+    lat, lab = g.latents_and_labels(int(z["seed"]), noise=meta["noise"],
+                                    flip_valid=meta["flip_valid"])
+    assert np.allclose([g.checksum(l) for l in lat], z["lat_checksums"], rtol=0, atol=1e-9)
+    assert np.allclose([g.checksum(l) for l in lab], z["label_checksums"], rtol=0, atol=1e-9)
+    return dict(meta["args"]), lat, lab, z, meta

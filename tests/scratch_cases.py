@@ -147,7 +147,7 @@ PROJECT_SLICES = (0, 2, 7, 57)            # 57 clamps to the K chunks at the nar
 PROJECT_ANCHOR = C.case_of((300, 8, 12, 7), 129)
 
 # ---------------------------------------------------------------- 4: derived images
-FUSED_TAIL_ROWS = (0, 2, 5)               # of tests/test_gpu_fused_tail.CASES
+FUSED_TAIL_ROWS = (0, 2, 5)               # of tests/fused_cases.CASES
 NARROW_FUSED = [(260, 76, 48, 20, 31, 3016), (280, 20, 8, 7, 64, 300)]  # of mmb2_cases.NARROW_FUSED
 WORD_TABLE_D = (15, 17, 299)
 WORD_TABLE_V = 33
@@ -157,7 +157,7 @@ SOLVE_MAX_D = 320
 
 
 def solve_cases():
-    """(n, d, npc) of tests/test_gpu_widths.SOLVE_CASES on the multi-workgroup solver."""
+    """(n, d, npc) of tests/widths_gpu.SOLVE_CASES on the multi-workgroup solver."""
     return [(n, d, npc) for n, d, npc in W.pc_cases() if npc in (1, 2) and 1 < d <= SOLVE_MAX_D]
 
 

@@ -43,7 +43,7 @@ NPCS = {"spike": (1, 2), "geom": (1, 2, 6), "mean": (1, 2, 3), "pair": (1, 2)}
 PAIR_SHAPES = [(4096, 300), (180, 300), (600, 400)]
 I8_SHAPES = [(4096, 300), (2048, 64)]
 
-FLOOR = (1e-12, 1e-10)  # first / later components: test_gpu_widths.SOLVE_BAR
+FLOOR = (1e-12, 1e-10)  # first / later components: width_cases.SOLVE_BAR
 CAP = 1e-9              # the project's PC bar everywhere
 MARGIN = 8.0
 EXEMPT_FROM_R = 1e8

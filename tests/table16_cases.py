@@ -55,6 +55,17 @@ def pair_rows(rows):
             for tn, tt in TABLE_TYPES for what, change, want in F.arg_rows(F.ALL_TYPES, rows)]
 
 
+def _ids(cases):
+    return [c[0].replace(" ", "_").replace(",", "") for c in cases]
+
+
+# the FusedStep keywords a 16-bit table's plan must not depend on: none, every
+# f32-frame front kernel asked for, every 16-bit-frame front kernel as well
+OVERRIDES = ({}, dict(stream_project=True, narrow_fused=True, split_stream=True),
+             dict(stream_project=True, narrow_fused=True, split_stream=True, fused_frames16=True,
+                  narrow_frames16=True, split_frames16=True))
+
+
 # ---------------------------------------------------------------- rounding
 @functools.lru_cache(maxsize=None)
 def table(case, kind):

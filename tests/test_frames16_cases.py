@@ -16,11 +16,8 @@ import torch
 import frames16_cases as F
 import mmb2_cases as C
 import mmb_lib
-import test_host_logic as H
-from frames16_cases import BF16, EINVAL, F16, F32, OK, P
+from frames16_cases import ARGS, BF16, EINVAL, F16, F32, OK, P, _shapes
 
-ARGS = ("ids table v wtab32 w_dense audio visual frame_type n t d a vd num_out s_out s_half aux_out "
-        "flag colmax colmax_ws stream").split()
 BASE = dict(ids=P, table=P, v=1000, wtab32=P, w_dense=None, audio=P, visual=P, frame_type=BF16, n=100,
             t=40, d=300, a=300, vd=300, num_out=P, s_out=P, s_half=1, aux_out=P, flag=None,
             colmax=None, colmax_ws=None, stream=None)
@@ -48,16 +45,6 @@ def test_stream_ft_argument_table_without_gpu(what, change, want):
 
 
 # ---------------------------------------------------------------- the plan
-def _shapes():
-    by_name = {}
-    for shape, kw, want in H._plan_cases():
-        key = (shape["n"], shape["t"], shape["a"], shape["vd"], shape["V"])
-        by_name.setdefault(key, shape)
-    want = {"c3": (1_000_000, 40, 300, 300, 400_000), "mosi": (1284, 20, 76, 48, 3016),
-            "pom": (100, 1089, 300, 300, 7763), "mid": (700, 40, 300, 300, 5000)}
-    return {name: by_name[key] for name, key in want.items()}
-
-
 @pytest.mark.parametrize("name", ["c3", "mosi", "pom", "mid"])
 def test_step_plan_with_16_bit_frames(name):
     import pipeline as PL

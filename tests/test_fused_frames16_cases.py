@@ -15,7 +15,6 @@ import pytest
 import frames16_cases as F
 import fused_frames16_cases as FF
 import mmb_lib
-import test_frames16_cases as T16
 
 KINDS = list(FF.KINDS)
 
@@ -53,7 +52,7 @@ def test_stream_project_ft_argument_table_without_gpu(what, change, want):
 def _plan(name):
     import pipeline as PL
 
-    shape = T16._shapes()[name]
+    shape = F._shapes()[name]
     shape = {"n_total": shape["n"], **shape}
     return lambda **kw: PL.step_plan(d=300, npc=1, cus=256, **shape, **kw)
 

@@ -20,7 +20,6 @@ import fused_table16_cases as FT16
 import large_cases as LC
 import mmb_lib
 import table16_cases as T
-import test_table16_cases as TT
 
 KINDS = list(FT16.KINDS)
 FRAMES = ("f32", "f16", "bf16")
@@ -79,7 +78,7 @@ def test_all_nine_pairs_are_in_the_table():
                        for c in FT16.ARG_CASES)
 
 
-@pytest.mark.parametrize("what,change,want", FT16.ARG_CASES, ids=TT._ids(FT16.ARG_CASES))
+@pytest.mark.parametrize("what,change,want", FT16.ARG_CASES, ids=T._ids(FT16.ARG_CASES))
 def test_stream_project_tt_argument_table_without_gpu(what, change, want):
     F.check_arg_row("mmb_mm2_stream_project_tt", FT16.ARGS, FT16.BASE, change, want)
 
@@ -88,13 +87,13 @@ def test_stream_project_tt_argument_table_without_gpu(what, change, want):
 def _plan(name):
     import pipeline as PL
 
-    shape = TT.TF._shapes()[name]
+    shape = F._shapes()[name]
     shape = {"n_total": shape["n"], **shape}
     return lambda **kw: PL.step_plan(d=300, npc=1, cus=256, **shape, **kw)
 
 
-# every override set of tests/test_table16_cases.py, and the ones a plan can differ by
-OVERRIDES = TT.OVERRIDES + (dict(stream_project=False), dict(chunks=3), dict(gram_kind="i8"),
+# every override set of tests/table16_cases.py, and the ones a plan can differ by
+OVERRIDES = T.OVERRIDES + (dict(stream_project=False), dict(chunks=3), dict(gram_kind="i8"),
                             dict(fused_frames16=True), dict(narrow_fused=False))
 
 

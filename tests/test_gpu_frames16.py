@@ -25,20 +25,15 @@ import frames16_cases as F
 import mmb2_cases as C
 import mmb_lib as L
 import pipeline as P
-from frames16_gpu import (_assert_graph_replays, _bufs, _check_oracle, _colmax_bufs, _dev, _networks, _off, _run,
-                          _step_inputs, _untouched)
+from frames16_gpu import (TWIN, _assert_graph_replays, _bufs, _check_oracle, _colmax_bufs, _dev, _networks, _off,
+                          _run, _step_inputs, _untouched)
+from mmb2_gpu import _is_narrow_route
 from oracle import mmb2_oracle as M
 
 pytestmark = pytest.mark.gpu
 
 MODES = ("ids+table", "ids+w")
 KIND_IDS = list(F.KINDS)
-
-
-def _is_narrow_route(case, mode, s_half):
-    D, A, Vd, T, N, V = case
-    return (mode == "ids+table" and s_half and 256 < D <= 512 and max(A, Vd) <= 128 and T <= 64
-            and D % 4 == A % 4 == Vd % 4 == 0)
 
 
 class _Launcher:
@@ -217,9 +212,6 @@ def test_fused_fronts_reject_16_bit_frames(gpu):
 
 
 # ------------------------------------------------------------------ C: the step
-TWIN = dict(stream_project=False, narrow_fused=False, split_stream=False)
-
-
 @pytest.mark.parametrize("kind", KIND_IDS)
 @pytest.mark.parametrize("dims", F.STEP, ids=C.shape_id)
 def test_fused_step_on_16_bit_frames(gpu, dims, kind):

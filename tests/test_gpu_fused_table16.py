@@ -30,16 +30,15 @@ import frames16_cases as F
 import frames16_gpu as G16
 import fused_table16_cases as FT16
 import large_cases as LC
+import large_gpu as LG  # the large cases' device fills and host copies
 import mmb2_cases as C
 import mmb_lib as L
 import models
 import pipeline as P
 import synth
 import table16_cases as T
-import test_gpu_large as TL            # the large cases' device fills and host copies
-import test_gpu_mmb2_widths as TM      # _frac, TOL: the bars of the large cases' row check
-import test_gpu_table16 as TG16        # the 16-bit-table step's twin inputs and oracle check
-from frames16_gpu import _assert_bit_for_bit, _bufs, _dev, _i32, _launch, _off
+from common_gpu import TOL, _flag, _frac  # the bars of the large cases' row check
+from frames16_gpu import TWIN, _assert_bit_for_bit, _bufs, _dev, _frames_of, _i32, _launch, _off
 from oracle import mmb2_oracle as M
 
 pytestmark = pytest.mark.gpu
@@ -182,7 +181,7 @@ def _step_inputs(case, kind, fkind, gpu):
     frames are of `fkind`, the same tensors in both."""
     z = C.inputs(case)
     E16 = _dev(T.table(case, kind), gpu)
-    au, vi = TG16._frames_of(case, fkind, "f32" if fkind == "f32" else "same", gpu)
+    au, vi = _frames_of(case, fkind, "f32" if fkind == "f32" else "same", gpu)
     base = {"wtab": _dev(z["wt32"], gpu), "ids": _dev(z["ids"], gpu, torch.int32), "audio": au, "visual": vi}
     return dict(base, table=E16), dict(base, table=E16.float())
 
@@ -206,7 +205,7 @@ def _step_pair(case, kind, fkind, gpu, **kw):
 
 
 def _check_oracle(case, kind, fkind, step, sif, mm2):
-    # (test_gpu_table16's check names the frames "f32" or "same": the oracle rows are per frame kind)
+    # (tests/test_gpu_table16.py's check names the frames "f32" or "same": the oracle rows are per frame kind)
     x = step.x.double().cpu().numpy()
     from oracle import sif_oracle as O
 
@@ -252,7 +251,7 @@ def test_without_the_opt_in_the_step_is_the_two_kernel_one(gpu, kind):
     inp16, inp32 = _step_inputs(case, kind, "f32", gpu)
     nets = G16._networks(case, gpu)
     off = P.FusedStep(inp16, nets)
-    assert off.plan == P.FusedStep(inp32, nets, **TG16.TWIN).plan
+    assert off.plan == P.FusedStep(inp32, nets, **TWIN).plan
     assert off.plan.front == "stream" and off.plan.split is False and off.s is not None
     assert P.FusedStep(inp16, nets, fused_table16=False).plan == off.plan
 
@@ -285,18 +284,18 @@ def _check_rows(c, inp, out, gpu, flag, what):
     torch.cuda.synchronize()
     assert int(flag.item()) == 0
     ids = inp["ids"].long()
-    text, sw = TL._host(inp["table"][ids]), TL._host(inp["wtab"][ids])
-    audio, visual = TL._host(inp["audio"]), TL._host(inp["visual"])
+    text, sw = LG._host_upcast(inp["table"][ids]), LG._host_upcast(inp["wtab"][ids])
+    audio, visual = LG._host_upcast(inp["audio"]), LG._host_upcast(inp["visual"])
     ref = C.stream_reference(text, text, sw, audio, visual)
     a = aux.cpu().numpy()
     assert np.array_equal(a[0], ref["cnt"])
-    fx = TM._frac(np.abs(x.cpu().numpy() - ref["x"]), C.sum_bar(z["t"], ref["x_abs"]))
-    fw = TM._frac(np.abs(a[1] - ref["sw"]), C.sum_bar(z["t"], ref["sw_abs"]))
+    fx = _frac(np.abs(x.cpu().numpy() - ref["x"]), C.sum_bar(z["t"], ref["x_abs"]))
+    fw = _frac(np.abs(a[1] - ref["sw"]), C.sum_bar(z["t"], ref["sw_abs"]))
     oracle = M.estimate_embedding_overall_gpu2(M.concat_inputs(text, audio, visual),
                                                C.params(z["d"], z["a"], z["vd"]), sw, text)
     got = mmb2.cpu().numpy()
     assert np.isfinite(got).all()
-    fo = M.row_rel_err(got, oracle) / TM.TOL
+    fo = M.row_rel_err(got, oracle) / TOL
     print(f"{c.name}, {what}: x {fx:.3f} and weight sum {fw:.3f} of sum_bar, MMB2 rows {fo:.3f} of 1e-5")
     assert fx <= 1.0 and fw <= 1.0 and fo < 1.0
 
@@ -314,24 +313,24 @@ def test_descriptor_guard_on_a_2_gib_bf16_table(gpu):
     dims = (z["n"], z["t"], z["d"], z["a"], z["vd"])
     assert P.stream_project_supported(*dims[1:]) and z["t"] >= 21
     torch.cuda.empty_cache()
-    table = TL._word_table(z["v"], z["d"], TL._gen(c, gpu), gpu, dtype=torch.bfloat16)
+    table = LG._word_table(z["v"], z["d"], LG._gen(c, gpu), gpu, dtype=torch.bfloat16)
     assert table.numel() * table.element_size() == LC.B31 and last.dims["v"] == z["v"] - 1
     ids_small = LC.gather_ids(last, z["n"], z["t"])
     assert ids_small.max() == z["v"] - 2
-    inp = TL._stream_inputs(c, gpu, table=table, ids=TL._dev(ids_small, gpu, torch.int32))
-    proj = TL._projection(c, gpu)
+    inp = LG._stream_inputs(c, gpu, table=table, ids=_dev(ids_small, gpu, torch.int32))
+    proj = LG._projection(c, gpu)
     outs = []
     for v in (z["v"] - 1, z["v"]):
-        flag = TL._flag(gpu)
+        flag = _flag(gpu)
         out = P.mm2_stream_project_tt(*dims, inp["audio"], inp["visual"], proj, ids32=inp["ids"], table=table[:v],
                                       wtab32=inp["wtab"][:v], flag=flag)
         _check_rows(last if v < z["v"] else c, inp, out, gpu, flag, f"V = {v}")
         outs.append(out)
     for a, b in zip(*outs):
         assert torch.equal(a, b)
-    inp["ids"] = TL._dev(LC.gather_ids(c, z["n"], z["t"]), gpu, torch.int32)
+    inp["ids"] = _dev(LC.gather_ids(c, z["n"], z["t"]), gpu, torch.int32)
     assert int(inp["ids"].max()) == z["v"] - 1
-    flag = TL._flag(gpu)
+    flag = _flag(gpu)
     out = P.mm2_stream_project_tt(*dims, inp["audio"], inp["visual"], proj, ids32=inp["ids"], table=table,
                                   wtab32=inp["wtab"], flag=flag)
     _check_rows(c, inp, out, gpu, flag, "the last table row")

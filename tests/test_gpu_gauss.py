@@ -53,18 +53,15 @@ import torch
 import gauss_cases as G
 import latent as LT
 import losses
+import gauss_gpu
 import mmb_lib as L
+from common_gpu import Ledger
+from common_gpu import _dev32 as _dev  # float32 unless told otherwise
 
 pytestmark = pytest.mark.gpu
 
-_WORST = {}
-
-
-def _note(what, ratio):
-    w = _WORST.setdefault(what, [0, 0.0])
-    w[0] += 1
-    w[1] = max(w[1], float(ratio))
-    return float(ratio)
+_WORST = Ledger()
+_note = _WORST.note  # (what, ratio)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -75,23 +72,9 @@ def _report():
     print()
 
 
-def _dev(a, gpu, dtype=torch.float32):
-    if a is None:
-        return None
-    return torch.as_tensor(np.array(a)).to(dtype).to(gpu).contiguous()  # (a copy: the cached inputs are read-only)
-
-
 def within(what, got, ref, bar):
-    """Every entry within its bar; an entry whose bar is 0 (no frames) exact."""
-    got = np.asarray(got.detach().cpu() if torch.is_tensor(got) else got, np.float64)
-    ref, bar = np.asarray(ref), np.asarray(bar)
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert np.isfinite(got).all(), what
-    err, pos = np.abs(got - ref), bar > 0
-    assert (err[~pos] == 0).all(), what
-    r = _note(what, (err[pos] / bar[pos]).max() if pos.any() else 0.0)
-    print(f"{what}: {r:.3f} of the bar")
-    assert r <= 1.0, f"{what}: {r:.3f} of the bar"
+    """gauss_gpu.within, noted in this module's report."""
+    gauss_gpu.within(_note, what, got, ref, bar)
 
 
 def _bits(t):

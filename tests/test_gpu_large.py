@@ -30,38 +30,48 @@ import pytest
 import torch
 
 import gauss_cases as G
+import gauss_gpu as GG       # within(): gauss_cases' bars, entry by entry
 import large_cases as LC
 import latent as LT
 import mmb2_cases as C
+import mmb2_gpu as MG        # _check_stream / _dequant: the stream outputs against mmb2_cases' bars
 import mmb_lib as L
 import pipeline as P
 import regressor_cases as RC
-import synth
-import test_gpu_gauss as TG              # within(): gauss_cases' bars, entry by entry
-import test_gpu_mmb2_widths as TM        # _check_stream / _dequant: the stream outputs against mmb2_cases' bars
-import test_gpu_regressor_widths as RW   # _check (regressor_cases' bounds, doubled), _launch_train, FLOOR
-import test_gpu_widths as TW             # F32_ROW, _check_gram, _check_gram_i8
-import test_gpu_word_widths as WW        # lp_ratio, grad_ratio
+import regressor_gpu as RG   # _check (regressor_cases' bounds, doubled), _launch_train
 import width_cases as W
-import word_cases as WC
+import widths_gpu as WG      # _check_gram, _check_gram_i8
+import word_cases as WC      # lp_ratio, grad_ratio
+from common_gpu import F32_ROW, TOL, Ledger, _dev, _flag, _frac, _networks, _unnoted
+from large_gpu import _gen, _host_upcast, _projection, _rand, _randn, _stream_inputs, _weights, _word_table
 from oracle import mmb2_oracle as M
 from oracle import regressor_oracle as R
 
 pytestmark = pytest.mark.gpu
 
-_WORST = {}  # case -> {what: largest error as a fraction of its bar}
+_WORST = Ledger()  # (case name, what) -> [comparisons, largest error as a fraction of its bar]
 
 
 def _note(case, what, frac):
-    w = _WORST.setdefault(case.name, {})
-    w[what] = max(w.get(what, 0.0), float(frac))
-    return float(frac)
+    return _WORST.note((case.name, what), frac)
+
+
+def _noter(case):
+    """The `note` handed to a shared checker, (group, what, fraction) or (group,
+    what, error, bar): recorded under the case, as a fraction of the bar."""
+    def note(group, what, value, bar=None):
+        _note(case, what if bar is None else f"{what} (of {bar:g})", value if bar is None else value / bar)
+        return float(value)
+    return note
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _report():
     yield
-    for name, w in _WORST.items():
+    by_case = {}
+    for (name, what), (_, frac) in _WORST.items():
+        by_case.setdefault(name, {})[what] = frac
+    for name, w in by_case.items():
         c = LC.CASES[name]
         op = c.op(c.crossing)
         print(f"\nlarge {name}: {c.crossing} {op.rows} x {op.row_bytes} B = {op.nbytes} B; " +
@@ -86,85 +96,26 @@ def _case(name, gpu):
     return c
 
 
-def _gen(c, gpu):
-    g = torch.Generator(device=gpu)
-    g.manual_seed(LC.seed_of(c))
-    return g
-
-
-def _rand(shape, g, gpu, dtype=torch.float32, lo=-1.0, hi=1.0):
-    """U(lo, hi) filled on the device, in the storage type itself."""
-    return torch.empty(shape, dtype=dtype, device=gpu).uniform_(lo, hi, generator=g)
-
-
-def _randn(shape, g, gpu, dtype=torch.float32, mean=0.0, std=1.0):
-    return torch.empty(shape, dtype=dtype, device=gpu).normal_(mean, std, generator=g)
-
-
-def _dev(a, gpu, dtype=None):
-    t = torch.as_tensor(np.array(a))  # (a copy: cached inputs are read-only)
-    return (t if dtype is None else t.to(dtype)).to(gpu)
-
-
-def _host(t):
-    return t.float().cpu().numpy() if t.dtype in (torch.float16, torch.bfloat16) else t.cpu().numpy()
-
-
-def _word_table(v, d, g, gpu, dtype=torch.float32):
-    """synth.word_table's family on the device: 0.4 N(0, 1) + 0.3 g, row 0 zero."""
-    table = _randn((v, d), g, gpu, dtype, 0.0, 0.4)
-    table.add_((0.3 * torch.randn(d, generator=g, device=gpu)).to(dtype))
-    table[0].zero_()
-    return table
-
-
-def _weights(v, g, gpu):
-    """SIF weights of a small vocabulary (synth.sif_weights); seeded U(0.05, 1) of a large one."""
-    if v <= 2 ** 16:
-        return _dev(synth.sif_weights(v, w0=1.0).astype(np.float32), gpu)
-    return _rand((v,), g, gpu, lo=0.05, hi=1.0)
-
-
-def _flag(gpu):
-    return torch.zeros(1, dtype=torch.int32, device=gpu)
-
-
 def _assert_sampled(c, rows):
     assert len(rows) <= LC.MAX_SAMPLE and rows[0] == 0 and rows[-1] == c.n - 1
 
 
 # ------------------------------------------------------------------ 1, 2, 4: the stream kernels
-FRAME_DTYPE = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
-
-
-def _stream_inputs(c, gpu, table=None, ids=None):
-    z = c.dims
-    g = _gen(c, gpu)
-    ft = FRAME_DTYPE[z.get("frames", "f32")]
-    if table is None:
-        table = _word_table(z["v"], z["d"], g, gpu)
-    if ids is None:
-        ids = torch.randint(0, z["v"], (z["n"], z["t"]), generator=g, device=gpu, dtype=torch.int32)
-    return {"table": table, "wtab": _weights(z["v"], g, gpu), "ids": ids,
-            "audio": _rand((z["n"], z["t"], z["a"]), g, gpu, ft),
-            "visual": _rand((z["n"], z["t"], z["vd"]), g, gpu, ft)}
-
-
 def _stream_check(c, inp, out, rows, s_half, gpu, flag):
     """x, s and aux of the sampled rows against mmb2_cases.stream_reference of
-    those rows' inputs (test_gpu_mmb2_widths._check_stream: sum_bar)."""
+    those rows' inputs (mmb2_gpu._check_stream: sum_bar)."""
     z = c.dims
     num, s, aux = out
     torch.cuda.synchronize()
     assert int(flag.item()) == 0
     ridx = torch.as_tensor(rows, device=gpu)
     ids = inp["ids"][ridx].long()
-    text = _host(inp["table"][ids])          # [k, t, d] gathered on the device: the rows the kernel read
-    sw = _host(inp["wtab"][ids])
-    ref = C.stream_reference(text, text, sw, _host(inp["audio"][ridx]), _host(inp["visual"][ridx]))
+    text = _host_upcast(inp["table"][ids])          # [k, t, d] gathered on the device: the rows the kernel read
+    sw = _host_upcast(inp["wtab"][ids])
+    ref = C.stream_reference(text, text, sw, _host_upcast(inp["audio"][ridx]), _host_upcast(inp["visual"][ridx]))
     got = (num[ridx].cpu().numpy(), s[ridx].cpu().numpy(), aux[:, ridx].cpu().numpy(), None)
     small = (z["d"], z["a"], z["vd"], z["t"], len(rows), z["v"])
-    frac = TM._check_stream(0, small, got, ref, s_half)
+    frac = MG._check_stream(_noter(c), 0, small, got, ref, s_half)
     _note(c, "stream outputs", frac)
     print(f"{c.name}: {len(rows)} rows, largest error {frac:.3f} of its bar (mmb2_cases.sum_bar)")
     return frac
@@ -250,25 +201,20 @@ def _fused_check(c, inp, out, rows, gpu, flag, what="MMB2 rows"):
     assert int(flag.item()) == 0
     ridx = torch.as_tensor(rows, device=gpu)
     ids = inp["ids"][ridx].long()
-    text, sw = _host(inp["table"][ids]), _host(inp["wtab"][ids])
-    audio, visual = _host(inp["audio"][ridx]), _host(inp["visual"][ridx])
+    text, sw = _host_upcast(inp["table"][ids]), _host_upcast(inp["wtab"][ids])
+    audio, visual = _host_upcast(inp["audio"][ridx]), _host_upcast(inp["visual"][ridx])
     ref = C.stream_reference(text, text, sw, audio, visual)
     a = aux[:, ridx].cpu().numpy()
     assert np.array_equal(a[0], ref["cnt"])
-    fx = _note(c, "x", TM._frac(np.abs(x[ridx].cpu().numpy() - ref["x"]), C.sum_bar(z["t"], ref["x_abs"])))
-    fw = _note(c, "weight sum", TM._frac(np.abs(a[1] - ref["sw"]), C.sum_bar(z["t"], ref["sw_abs"])))
+    fx = _note(c, "x", _frac(np.abs(x[ridx].cpu().numpy() - ref["x"]), C.sum_bar(z["t"], ref["x_abs"])))
+    fw = _note(c, "weight sum", _frac(np.abs(a[1] - ref["sw"]), C.sum_bar(z["t"], ref["sw_abs"])))
     oracle = M.estimate_embedding_overall_gpu2(M.concat_inputs(text, audio, visual),
                                                C.params(z["d"], z["a"], z["vd"]), sw, text)
     got = mmb2[ridx].cpu().numpy()
     assert np.isfinite(got).all()
-    fo = _note(c, what + " (of 1e-5)", M.row_rel_err(got, oracle) / TM.TOL)
+    fo = _note(c, what + " (of 1e-5)", M.row_rel_err(got, oracle) / TOL)
     print(f"{c.name}: {len(rows)} rows, x {fx:.3f} and weight sum {fw:.3f} of sum_bar, {what} {fo:.3f} of 1e-5")
     assert fx <= 1.0 and fw <= 1.0 and fo < 1.0
-
-
-def _projection(c, gpu):
-    z = c.dims
-    return P.MMB2Projection(TM._networks((z["d"], z["a"], z["vd"]), gpu), z["d"], z["a"], z["vd"], z["t"], gpu)
 
 
 @pytest.mark.parametrize("name", ["fused_visual", "fused_audio", "fused_ft_f16_visual"])
@@ -353,7 +299,7 @@ def test_narrow_fused(gpu, name):
 def _wavg_check(c, table, wtab, ids, got_x, got_num, got_cnt, rows, gpu):
     ridx = torch.as_tensor(rows, device=gpu)
     tok = ids[ridx].long()
-    x, num, cnt = LC.wavg_reference(_host(table[tok]), _host(wtab[tok]))
+    x, num, cnt = LC.wavg_reference(_host_upcast(table[tok]), _host_upcast(wtab[tok]))
     fr = []
     if got_x is not None:
         fr.append(_note(c, "x (of 2e-6)", M.row_rel_err(got_x[ridx].cpu().numpy(), x) / 2e-6))
@@ -432,10 +378,10 @@ def test_gram_routes(gpu, name):
     x, rows, vals = _planted(c, gpu)
     cnt = cnt_h = None
     if c.dims["cnt"]:
-        cnt_h = TW._counts(len(rows), LC.seed_of(c))
+        cnt_h = WG._counts(len(rows), LC.seed_of(c))
         cnt = torch.ones(c.n, device=gpu)
         cnt[torch.as_tensor(rows, device=gpu)] = _dev(cnt_h, gpu)
-    e = TW._check_gram(P.gram(x, cnt), LC.gram_reference(vals, cnt_h), name)
+    e = WG._check_gram(_unnoted, P.gram(x, cnt), LC.gram_reference(vals, cnt_h), name)
     _note(c, "G (of 1e-13)", e / 1e-13)
     print(f"{name}: {len(rows)} planted rows, |G - exact| / max |G| = {e:.3e} (bar 1e-13)")
 
@@ -447,7 +393,7 @@ def test_gram_f64(gpu):
     g = torch.empty((c.dims["d"],) * 2, dtype=torch.float64, device=gpu)
     ws = P.GramWorkspace(c.n, c.dims["d"], gpu)
     L.call("mmb_gram_f64", L.ptr(x), c.n, c.dims["d"], L.ptr(g), 0, L.ptr(ws.buf), L.stream_ptr())
-    e = TW._check_gram(g, LC.gram_reference(vals), c.name)
+    e = WG._check_gram(_unnoted, g, LC.gram_reference(vals), c.name)
     _note(c, "G (of 1e-13)", e / 1e-13)
     print(f"gram_f64: |G - exact| / max |G| = {e:.3e} (bar 1e-13)")
 
@@ -467,7 +413,7 @@ def test_gram_part_and_finish(gpu):
         for i, (r0, r1) in enumerate(blocks):
             L.call("mmb_gram_part", L.ptr(x[r0:r1]), None, r1 - r0, n, d, int(i > 0), L.ptr(ws.buf), L.stream_ptr())
         L.call("mmb_gram_finish", n, d, L.ptr(g), 0, L.ptr(ws.buf), L.stream_ptr())
-        e = TW._check_gram(g, ref, (c.name, len(blocks)))
+        e = WG._check_gram(_unnoted, g, ref, (c.name, len(blocks)))
         _note(c, "G (of 1e-13)", e / 1e-13)
         print(f"gram_part_finish, {len(blocks)} block(s): |G - exact| / max |G| = {e:.3e} (bar 1e-13)")
 
@@ -479,7 +425,7 @@ def test_gram_i8(gpu):
     cm = P.colmax(x)
     assert np.array_equal(cm.cpu().numpy().view(np.float32), np.abs(vals).max(0).astype(np.float32))
     g = P.gram_i8(x, cm).cpu().numpy()
-    TW._check_gram_i8(g, vals.astype(np.float32))
+    WG._check_gram_i8(_noter(c), g, vals.astype(np.float32))
     exact = LC.gram_reference(vals)
     _note(c, "G vs exact (of 2e-9)", np.abs(g - exact).max() / np.abs(exact).max() / 2e-9)
 
@@ -512,7 +458,7 @@ def test_remove(gpu, name):
     if out_dtype == torch.float64:
         e = _note(c, "f64 out (of 1e-12)", M.row_rel_err(got, ref) / 1e-12)
     else:
-        e = _note(c, "f32 out (of 2^-23 of the row's max)", LC.row_err(got, ref).max() / TW.F32_ROW)
+        e = _note(c, "f32 out (of 2^-23 of the row's max)", LC.row_err(got, ref).max() / F32_ROW)
     print(f"{name}: {len(rows)} rows, largest error {e:.3f} of its bar")
     assert e < 1.0 if out_dtype == torch.float64 else e <= 1.0
     # the route does not depend on n: a compact copy of the sampled rows gives the same bits
@@ -531,7 +477,7 @@ def _project_operands(c, gpu, s_half):
                                ids32=inp["ids"], table=inp["table"], wtab32=inp["wtab"], flag=flag, s_half=s_half)
     torch.cuda.synchronize()
     assert int(flag.item()) == 0 and s.numel() * s.element_size() == c.op("s").nbytes > LC.B32
-    proj = P.MMB2Projection(TM._networks((z["d"], z["a"], z["vd"]), gpu), z["d"], z["a"], z["vd"], z["t"], gpu)
+    proj = P.MMB2Projection(_networks((z["d"], z["a"], z["vd"]), gpu), z["d"], z["a"], z["vd"], z["t"], gpu)
     return inp, num, s, aux, proj
 
 
@@ -545,8 +491,8 @@ def _project_check(c, what, got, s_rows, num, aux, proj, ridx, x3, oracle):
     g = got[ridx].cpu().numpy().astype(np.float64)
     err = LC.row_err(g, ref)
     e = _note(c, what + " (of beta)", (err / bar).max())
-    f = _note(c, what + " (of 1e-5)", err.max() / TM.TOL)
-    o = _note(c, what + " vs oracle (of 1e-5)", M.row_rel_err(g, oracle) / TM.TOL)
+    f = _note(c, what + " (of 1e-5)", err.max() / TOL)
+    o = _note(c, what + " vs oracle (of 1e-5)", M.row_rel_err(g, oracle) / TOL)
     print(f"{c.name} {what}: {e:.3f} of beta, {f:.3f} of 1e-5, oracle {o:.3f} of 1e-5")
     assert e <= 1.0 and f < 1.0 and o < 1.0, (what, e, f, o)
 
@@ -554,8 +500,8 @@ def _project_check(c, what, got, s_rows, num, aux, proj, ridx, x3, oracle):
 def _oracle_rows(c, inp, ridx):
     z = c.dims
     ids = inp["ids"][ridx].long()
-    text, sw = _host(inp["table"][ids]), _host(inp["wtab"][ids])
-    data = M.concat_inputs(text, _host(inp["audio"][ridx]), _host(inp["visual"][ridx]))
+    text, sw = _host_upcast(inp["table"][ids]), _host_upcast(inp["wtab"][ids])
+    data = M.concat_inputs(text, _host_upcast(inp["audio"][ridx]), _host_upcast(inp["visual"][ridx]))
     return M.estimate_embedding_overall_gpu2(data, C.params(z["d"], z["a"], z["vd"]), sw, text)
 
 
@@ -583,7 +529,7 @@ def test_project_x3(gpu):
     oracle = _oracle_rows(c, inp, ridx)
     del inp
     torch.cuda.empty_cache()
-    s_rows = TM._dequant(s[ridx], aux[:, ridx], proj.kp)
+    s_rows = MG._dequant(s[ridx], aux[:, ridx], proj.kp)
     got = P.mm2_project(s, num, aux, proj)
     _project_check(c, "mmb_mm2_project_x3", got, s_rows, num, aux, proj, ridx, True, oracle)
     pch = W.orthonormal_rows(1, z["d"], seed=z["d"])
@@ -593,7 +539,7 @@ def test_project_x3(gpu):
     sif = torch.full((c.n, z["d"]), -7.0, device=gpu)
     got_pc = P.mm2_project(s, num, aux, proj, pc=pc, sif_out=sif)
     assert torch.equal(got_pc[ridx], got[ridx])  # the removal does not touch the MMB2 rows
-    e = _note(c, "x3_rmpc sif_out (of 2^-23)", LC.row_err(sif[ridx].cpu().numpy(), removed).max() / TW.F32_ROW)
+    e = _note(c, "x3_rmpc sif_out (of 2^-23)", LC.row_err(sif[ridx].cpu().numpy(), removed).max() / F32_ROW)
     assert e <= 1.0
     del got_pc
     ws = P.project_split_ws(c.n, proj.kp, gpu, slices=z["slices"])
@@ -601,15 +547,20 @@ def test_project_x3(gpu):
     sif.fill_(-7.0)
     got_sp = P.mm2_project(s, num, aux, proj, pc=pc, sif_out=sif, split=ws, slices=z["slices"])
     _project_check(c, "mmb_mm2_project_x3_split", got_sp, s_rows, num, aux, proj, ridx, True, oracle)
-    e = _note(c, "x3_split sif_out (of 2^-23)", LC.row_err(sif[ridx].cpu().numpy(), removed).max() / TW.F32_ROW)
+    e = _note(c, "x3_split sif_out (of 2^-23)", LC.row_err(sif[ridx].cpu().numpy(), removed).max() / F32_ROW)
     assert e <= 1.0
 
 
 # ------------------------------------------------------------------ 11: the regressor
+def _mlp_check(c, key, what, got, ref, bound):
+    """regressor_gpu._check, its ratio noted under the case as `key`."""
+    return _note(c, key, RG._check(_unnoted, "large", what, got, ref, bound))
+
+
 def _mlp_params(c, gpu, seed=0):
     z = c.dims
     prm = RC.make_params(np.random.default_rng([z["d"], z["h"], z["o"], seed]), z["d"], z["h"], z["o"])
-    dev = [RW._dev(p, gpu) for p in prm]
+    dev = [RG._dev(p, gpu) for p in prm]
     assert dev[0].data_ptr() % 16 == 0
     return prm, dev
 
@@ -630,28 +581,26 @@ def test_mlp_forward_idx_and_eval_perm(gpu):
     rows = LC.gather_ids(c, fc.b, 1).ravel()
     assert set(LC.table_rows(c, fc.b)) == set(rows) and len(set(rows)) == fc.b and rows.max() == z["v"] - 1
     idx = _dev(rows, gpu)
-    lat[idx], lab[idx] = RW._dev(ref["x"], gpu), RW._dev(ref["labels"], gpu)
-    keep = [RW._dev(p, gpu) for p in ref["params"]]
+    lat[idx], lab[idx] = RG._dev(ref["x"], gpu), RG._dev(ref["labels"], gpu)
+    keep = [RG._dev(p, gpu) for p in ref["params"]]
     assert keep[0].data_ptr() % 16 == 0
     pp = [L.ptr(p) for p in keep]
     st = L.stream_ptr()
     y = torch.full((fc.b, fc.o), np.nan, device=gpu)
     L.call("mmb_mlp_forward", L.ptr(lat), L.ptr(idx), fc.b, fc.d, fc.h, fc.o, *pp, L.ptr(y), st)
-    _note(c, "mmb_mlp_forward idx", RW._check("large", "mmb_mlp_forward idx", RW._host(y), ref["y"], ref["y_bound"]))
+    _mlp_check(c, "mmb_mlp_forward idx", "mmb_mlp_forward idx", RG._host64(y), ref["y"], ref["y_bound"])
     batch = 3
     bl = torch.full((-(-fc.b // batch),), np.nan, device=gpu)
     pred = torch.full((fc.b, fc.o), np.nan, device=gpu)
     L.call("mmb_mlp_eval", L.ptr(lat), L.ptr(lab), L.ptr(idx), fc.b, batch, fc.d, fc.h, fc.o, *pp, L.ptr(bl),
            L.ptr(pred), st)
-    _note(c, "mmb_mlp_eval perm pred", RW._check("large", "mmb_mlp_eval perm pred", RW._host(pred), ref["y"],
-                                                 ref["y_bound"]))
+    _mlp_check(c, "mmb_mlp_eval perm pred", "mmb_mlp_eval perm pred", RG._host64(pred), ref["y"], ref["y_bound"])
     # the batch losses as tests/test_gpu_regressor_widths.py derives them
     diff = np.abs(ref["y"] - ref["labels"])
     want = np.array([diff[s:s + batch].mean() for s in range(0, fc.b, batch)])
     m = np.array([diff[s:s + batch].size for s in range(0, fc.b, batch)])
     bound = np.array([ref["y_bound"][s:s + batch].mean() for s in range(0, fc.b, batch)]) + (m + 2) * RC.U32 * want
-    _note(c, "mmb_mlp_eval perm batch_loss", RW._check("large", "mmb_mlp_eval perm batch_loss", RW._host(bl), want,
-                                                       bound))
+    _mlp_check(c, "mmb_mlp_eval perm batch_loss", "mmb_mlp_eval perm batch_loss", RG._host64(bl), want, bound)
 
 
 @pytest.mark.parametrize("name", ["mlp_rows_x", "mlp_rows_hid"])
@@ -676,22 +625,22 @@ def test_mlp_forward_train_and_backward(gpu, name):
     ridx = torch.as_tensor(rows, device=gpu)
     xs = x[ridx].double().cpu().numpy()
     ry, pre, rhid = R.mlp_forward(xs, *prm)
-    _note(c, "y", RW._check("large", name + " y", RW._host(y[ridx]), ry, R.out_bound(xs, *prm)))
-    _note(c, "hid", RW._check("large", name + " hid", RW._host(hid[ridx]), rhid, R.pre_bound(xs, *prm[:2])))
+    _mlp_check(c, "y", name + " y", RG._host64(y[ridx]), ry, R.out_bound(xs, *prm))
+    _mlp_check(c, "hid", name + " hid", RG._host64(hid[ridx]), rhid, R.pre_bound(xs, *prm[:2]))
     # backward: dy planted on the sampled rows
     dys = RC.f32(np.random.default_rng(LC.seed_of(c)).standard_normal((len(rows), o)))
     dy = torch.zeros((n, o), device=gpu)
-    dy[ridx] = RW._dev(dys, gpu)
+    dy[ridx] = RG._dev(dys, gpu)
     dh, dx = torch.empty((n, h), device=gpu), torch.empty((n, d), device=gpu)
     params = name == "mlp_rows_x"  # (h + 1 blocks walk all rows: at h = 2040 the row kernels alone)
     grads = {k: torch.full(s, np.nan, device=gpu) if params else None
              for k, s in (("dw1", (h, d)), ("db1", (h,)), ("dw2", (o, h)), ("db2", (o,)))}
     L.call("mmb_mlp_backward", L.ptr(x), L.ptr(hid), n, d, h, o, pp[0], pp[2], L.ptr(dy), L.ptr(dh), L.ptr(dx),
            *[L.ptr(grads[k]) for k in ("dw1", "db1", "dw2", "db2")], st)
-    hid_s = RW._host(hid[ridx])  # the activations the backward was given
+    hid_s = RG._host64(hid[ridx])  # the activations the backward was given
     ref, bounds = RC.backward_bounds(xs, hid_s, prm[0], prm[2], dys)
     for k, t in (("dh", dh[ridx]), ("dx", dx[ridx])) + tuple((k, grads[k]) for k in grads if params):
-        _note(c, k, RW._check("large", f"{name} {k}", RW._host(t), ref[k], bounds[k]))
+        _mlp_check(c, k, f"{name} {k}", RG._host64(t), ref[k], bounds[k])
     others = torch.as_tensor(np.setdiff1d(LC._fill(set(), n, 5, 32), rows), device=gpu)
     assert not dh[others].cpu().numpy().any() and not dx[others].cpu().numpy().any()
 
@@ -714,27 +663,27 @@ def test_mlp_train_rows_past_the_boundaries(gpu):
     rows = LC.gather_ids(c, tc.n, 1).ravel()
     assert len(set(rows)) == tc.n and rows.max() == z["v"] - 1 and (rows * z["d"] * 4 > LC.B31).sum() >= 4
     idx = _dev(rows, gpu)
-    lat[idx], lab[idx] = RW._dev(inp["x"], gpu), RW._dev(inp["y"], gpu)
-    prm = [RW._dev(p, gpu) for p in inp["params"]]
+    lat[idx], lab[idx] = RG._dev(inp["x"], gpu), RG._dev(inp["y"], gpu)
+    prm = [RG._dev(p, gpu) for p in inp["params"]]
     perm = _dev(rows[inp["perm"]], gpu)
     spe = -(-tc.n // tc.batch)
     sl = torch.full((RC.N_EPOCHS * spe,), np.nan, device=gpu)
     flag = _flag(gpu)
-    ws = RW._workspace(gpu, tc.d, tc.h)
+    ws = RG._workspace(gpu, tc.d, tc.h)
     rc = L.query("mmb_mlp_train", L.ptr(lat), L.ptr(lab), L.ptr(perm), tc.n, RC.N_EPOCHS, tc.batch, tc.d, tc.h,
                  tc.o, RC.LR, *[L.ptr(p) for p in prm], L.ptr(sl), None, None, None, 0, 1, tc.epoch0, None,
                  L.ptr(ws), L.ptr(flag), L.stream_ptr())
     torch.cuda.synchronize()
     assert rc == 0 and int(flag.item()) == 0 and not ws[:4].any().item()
-    got = {"params": [RW._host(p) for p in prm], "step_loss": RW._host(sl), "valid_loss": np.zeros(0)}
+    got = {"params": [RG._host64(p) for p in prm], "step_loss": RG._host64(sl), "valid_loss": np.zeros(0)}
     env_p, env_l = RC.f32_envelope(tc)
     dev_p, dev_l = RC.rel_dev(got, ref)
-    bar_p, bar_l = max(4 * env_p, RW.FLOOR), max(4 * env_l, RW.FLOOR)
+    bar_p, bar_l = max(4 * env_p, RC.FLOOR), max(4 * env_l, RC.FLOOR)
     _note(c, "parameters", dev_p / bar_p)
     _note(c, "losses", dev_l / bar_l)
     print(f"mlp_train: parameters {dev_p:.2e} (bar {bar_p:.2e}), losses {dev_l:.2e} (bar {bar_l:.2e})")
     assert dev_p <= bar_p and dev_l <= bar_l
-    rc2, prm2, sl2, _, flag2 = RW._launch_train(gpu, tc, inp, ws)  # the compact rows: the same bits
+    rc2, prm2, sl2, _, flag2 = RG._launch_train(gpu, tc, inp, ws)  # the compact rows: the same bits
     assert rc2 == 0 and torch.equal(sl2, sl) and all(torch.equal(a, b) for a, b in zip(prm, prm2))
 
 
@@ -758,19 +707,24 @@ def test_word_logprob_workspace(gpu):
     lat = _randn((n, d), g, gpu, std=0.5)
     ids = torch.randint(0, v, (n, l), generator=g, device=gpu, dtype=torch.int32)
     w, mask, up = _rand((n, l), g, gpu, lo=0.05, hi=1.0), torch.ones((n, l), device=gpu), torch.zeros(n, device=gpu)
-    lat[ridx], ids[ridx] = RW._dev(inp["lat"], gpu), _dev(inp["ids"], gpu, torch.int32)
-    w[ridx], mask[ridx], up[ridx] = (RW._dev(inp[k], gpu) for k in ("w", "mask", "up"))
-    wt = LT.WordTable(RW._dev(inp["table"], gpu))
+    lat[ridx], ids[ridx] = RG._dev(inp["lat"], gpu), _dev(inp["ids"], gpu, torch.int32)
+    w[ridx], mask[ridx], up[ridx] = (RG._dev(inp[k], gpu) for k in ("w", "mask", "up"))
+    wt = LT.WordTable(RG._dev(inp["table"], gpu))
     x = lat.requires_grad_(True)
     lp = LT.word_log_prob(x, wt, w, mask, WC.A, ids=ids)
     (lp * up).sum().backward()
-    r1 = _note(c, "lp", WW.lp_ratio(lp.detach()[ridx].cpu(), lp_ref))
-    r2 = _note(c, "gradient", WW.grad_ratio(x.grad[ridx].cpu(), g_ref))
+    r1 = _note(c, "lp", WC.lp_ratio(lp.detach()[ridx].cpu(), lp_ref))
+    r2 = _note(c, "gradient", WC.grad_ratio(x.grad[ridx].cpu(), g_ref))
     print(f"word_logprob: lp {r1:.3f} and gradient {r2:.3f} of their bars")
     assert r1 <= 1.0 and r2 <= 1.0 and bool(torch.isfinite(lp).all())
 
 
 # (the other latent kernels)
+def _within(c, key, what, got, ref, bar):
+    """gauss_gpu.within, its fraction noted under the case as `key`."""
+    GG.within(lambda _, ratio: _note(c, key, ratio), what, got, ref, bar)
+
+
 @pytest.mark.parametrize("name", ["gauss_stats_x", "gauss_stats_mask"])
 def test_gauss_stats(gpu, name):
     c = _case(name, gpu)
@@ -787,9 +741,8 @@ def test_gauss_stats(gpu, name):
     ridx = torch.as_tensor(rows, device=gpu)
     xs, ms = x[ridx].contiguous(), None if mask is None else mask[ridx].contiguous()
     ref, bar = G.stats_reference(xs.double().cpu().numpy(), None if ms is None else ms.double().cpu().numpy())
-    TG.within(f"large {name}", st[ridx], ref, bar)
+    _within(c, "stats (gauss_cases.stats_reference)", f"large {name}", st[ridx], ref, bar)
     assert torch.equal(LT.gauss_stats(xs, ms).view(torch.int64), st[ridx].view(torch.int64))
-    _note(c, "stats (gauss_cases.stats_reference)", TG._WORST[f"large {name}"][1])
 
 
 def test_gauss_loglik_idx(gpu):
@@ -817,8 +770,7 @@ def test_gauss_loglik_idx(gpu):
     ref = G.normal_reference(mu, sigma, x, None, up)
     bars = G.normal_bars(mu, sigma, x, None, up, ref)
     for what, got, r, bar in zip(("lp", "dmu", "dsigma"), (lp[0], mus.grad, sgs.grad), ref, bars):
-        TG.within(f"large gauss {what}", got, r, bar)
-        _note(c, what, TG._WORST[f"large gauss {what}"][1])
+        _within(c, what, f"large gauss {what}", got, r, bar)
 
 
 def _ln_inputs(c, gpu, dy=None):
@@ -851,8 +803,7 @@ def test_layer_norm_backward_dx(gpu):
     _assert_sampled(c, rows)
     ridx = torch.as_tensor(rows, device=gpu)
     ref, bars = _ln_reference(dy, x, mean, rstd, gamma, ridx)
-    TG.within("large LN dx", dx[ridx], ref[0], bars[0])
-    _note(c, "dx", TG._WORST["large LN dx"][1])
+    _within(c, "dx", "large LN dx", dx[ridx], ref[0], bars[0])
 
 
 def test_layer_norm_backward_dgamma(gpu):
@@ -873,8 +824,7 @@ def test_layer_norm_backward_dgamma(gpu):
     # the planted rows alone: every other row adds an exact zero to its group's sums
     ref, bars = _ln_reference(dy, x, mean, rstd, gamma, ridx)
     for what, got, r, bar in zip(("dx", "dgamma", "dbeta"), (dx[ridx], dgamma, dbeta), ref, bars):
-        TG.within(f"large LN planted {what}", got, r, bar)
-        _note(c, what, TG._WORST[f"large LN planted {what}"][1])
+        _within(c, what, f"large LN planted {what}", got, r, bar)
     others = torch.as_tensor(np.setdiff1d(LC.sample_rows(c), rows), device=gpu)
     assert not dx[others].cpu().numpy().any()
 
@@ -898,7 +848,7 @@ def test_word_normalize(gpu):
     # pad is zero, and so is row 0 (a zero table row: 0 / 1e-8)
     assert not got[:, d:].any() and not got[0].any()
     bar = 2 * ((d + 1) / 2 + 2) * C.U * np.abs(ref)
-    e = _note(c, "Wn", TM._frac(np.abs(got - ref), bar))
+    e = _note(c, "Wn", _frac(np.abs(got - ref), bar))
     print(f"word_normalize: {len(rows)} rows, largest error {e:.3f} of its bar")
     assert e <= 1.0
     again = torch.empty((len(rows), dp), device=gpu)

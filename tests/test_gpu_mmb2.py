@@ -13,12 +13,11 @@ import models
 import pipeline as P
 import sif2
 import synth
+from mmb2_cases import TOL
 from oracle import mmb2_oracle as M
 from oracle import sif_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-5
 
 
 def _inputs(z, dev):

@@ -37,14 +37,13 @@ import models
 import narrow_frames16_cases as NF
 import pipeline as P
 import synth
-from frames16_gpu import _assert_bit_for_bit, _bufs, _i32, _launch
+from frames16_gpu import TOL, _assert_bit_for_bit, _bufs, _i32, _launch
 from oracle import mmb2_oracle as M
 from oracle import sif_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 KIND_IDS = list(NF.KINDS)
-TOL = 1e-5  # the end-to-end bar of tests/test_gpu_mmb2.py
 
 
 def _guarded(t16, extra=0):

@@ -201,7 +201,7 @@ def test_full_size_run_matches_reference(gpu, tmp_path, case, capsys):
     `envelope`).  So: the first 20 epochs within 1e-4; the early-stopping
     events, epoch count and files exactly; the loss curves and final metrics
     within 1.5x the reference's own rounding envelope."""
-    from test_regressor_oracle import full_case
+    from regressor_cases import full_case
 
     args, lat, lab, z, meta = full_case(case)
     captured = {}

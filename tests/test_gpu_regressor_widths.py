@@ -51,25 +51,22 @@ import torch
 
 import mmb_lib as L
 import regressor_cases as C
+import regressor_gpu as RG
 import sentiment_model as SM
+from common_gpu import Ledger
 from oracle import regressor_oracle as R
+from regressor_cases import FLOOR
+from regressor_gpu import _dev, _host64, _launch_train, _workspace
 
 pytestmark = pytest.mark.gpu
 
 MMB_EINVAL = -1
-FLOOR = 8 * 2.0 ** -24
 
-_WORST = {}  # (group, what) -> [comparisons, largest error / bar]
+_WORST = Ledger()  # (group, what) -> [comparisons, largest error / bar]
 
 
-def _note(group, what, err, bar):
-    """Record err / bar elementwise (bar 0 means the value must be exact)."""
-    err, bar = np.asarray(err, np.float64), np.broadcast_to(np.asarray(bar, np.float64), np.shape(err))
-    ratio = np.where(err == 0, 0.0, err / np.maximum(bar, 1e-300))
-    w = _WORST.setdefault((group, what), [0, 0.0])
-    w[0] += 1
-    w[1] = max(w[1], float(ratio.max()) if ratio.size else 0.0)
-    return float(ratio.max()) if ratio.size else 0.0
+def _note(group, what, ratio):
+    return _WORST.note((group, what), ratio)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -80,20 +77,9 @@ def _report():
     print()
 
 
-def _dev(a, gpu, dtype=torch.float32):
-    return torch.as_tensor(np.array(a)).to(dtype).to(gpu).contiguous()  # (a copy: the cached inputs are read-only)
-
-
-def _host(t):
-    return t.cpu().numpy().astype(np.float64)
-
-
 def _check(group, what, got, ref, bound):
-    """|got - ref| <= 2 bound, element by element."""
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    r = _note(group, what, np.abs(got - ref), 2 * bound)
-    assert r <= 1.0, f"{what}: {r:.3f} of the derived bar"
-    return r
+    """regressor_gpu._check, noted in this module's report."""
+    return RG._check(_note, group, what, got, ref, bound)
 
 
 FWD_IDS = [C.fwd_id(c) for c in C.FWD_CASES]
@@ -113,19 +99,19 @@ def test_forward_entry_points(gpu, c):
     st = L.stream_ptr()
     y = torch.full((c.b, c.o), np.nan, device=gpu)
     L.call("mmb_mlp_forward", L.ptr(x), None, c.b, c.d, c.h, c.o, *pp, L.ptr(y), st)
-    _check("a", "mmb_mlp_forward", _host(y), z["y"], z["y_bound"])
+    _check("a", "mmb_mlp_forward", _host64(y), z["y"], z["y_bound"])
     rng = np.random.default_rng(c.b)
     perm = rng.permutation(c.b)
     idx = _dev(perm, gpu, torch.int64)
     y = torch.full((c.b, c.o), np.nan, device=gpu)
     L.call("mmb_mlp_forward", L.ptr(x), L.ptr(idx), c.b, c.d, c.h, c.o, *pp, L.ptr(y), st)
-    _check("a", "mmb_mlp_forward idx", _host(y), z["y"][perm], z["y_bound"][perm])
+    _check("a", "mmb_mlp_forward idx", _host64(y), z["y"][perm], z["y_bound"][perm])
 
     y = torch.full((c.b, c.o), np.nan, device=gpu)
     hid = torch.full((c.b, c.h), np.nan, device=gpu)
     L.call("mmb_mlp_forward_train", L.ptr(x), c.b, c.d, c.h, c.o, *pp, L.ptr(y), L.ptr(hid), st)
-    _check("a", "mmb_mlp_forward_train y", _host(y), z["y"], z["y_bound"])
-    _check("a", "mmb_mlp_forward_train hid", _host(hid), z["hid"], z["pre_bound"])
+    _check("a", "mmb_mlp_forward_train y", _host64(y), z["y"], z["y_bound"])
+    _check("a", "mmb_mlp_forward_train hid", _host64(hid), z["hid"], z["pre_bound"])
 
     for order, batch, p_dev in ((np.arange(c.b), 4, None), (perm, 3, idx)):
         nb = -(-c.b // batch)
@@ -134,14 +120,14 @@ def test_forward_entry_points(gpu, c):
         L.call("mmb_mlp_eval", L.ptr(x), L.ptr(lab), L.ptr(p_dev), c.b, batch, c.d, c.h, c.o, *pp,
                L.ptr(bl), L.ptr(pred), st)
         what = "mmb_mlp_eval" + (" perm" if p_dev is not None else "")
-        _check("a", what + " pred", _host(pred), z["y"][order], z["y_bound"][order])
+        _check("a", what + " pred", _host64(pred), z["y"][order], z["y_bound"][order])
         diff = np.abs(z["y"] - z["labels"])[order]
         ref = np.array([diff[s:s + batch].mean() for s in range(0, c.b, batch)])
         # each |y - label| carries y's bound and one rounding; the sum of m terms m more, the division one
         m = np.array([diff[s:s + batch].size for s in range(0, c.b, batch)])
         bound = np.array([z["y_bound"][order][s:s + batch].mean() for s in range(0, c.b, batch)]) \
             + (m + 2) * C.U32 * ref
-        _check("a", what + " batch_loss", _host(bl), ref, bound)
+        _check("a", what + " batch_loss", _host64(bl), ref, bound)
 
 
 @pytest.mark.parametrize("want", ["all", "no_dx", "no_params"])
@@ -166,7 +152,7 @@ def test_backward_entry_point(gpu, c, want):
            L.ptr(dy), *[L.ptr(out[k]) for k in ("dh", "dx", "dw1", "db1", "dw2", "db2")], L.stream_ptr())
     for k, t in out.items():
         if t is not None:
-            _check("a", "mmb_mlp_backward " + k, _host(t), g[k], bounds[k])
+            _check("a", "mmb_mlp_backward " + k, _host64(t), g[k], bounds[k])
 
 
 # ------------------------------------------------------------------ b: mmb_mlp_train
@@ -215,15 +201,15 @@ def test_train_vs_float64_run(gpu, c):
     for a, b in zip(*runs):
         assert torch.equal(a, b), "second launch on the same workspace differs"
     nvl = C.n_validations(c) * -(-c.nv // c.batch) if c.nv else 0
-    got = {"params": [_host(p) for p in P], "step_loss": _host(sl),
-           "valid_loss": _host(vl)[:nvl] if nvl else np.zeros(0)}
+    got = {"params": [_host64(p) for p in P], "step_loss": _host64(sl),
+           "valid_loss": _host64(vl)[:nvl] if nvl else np.zeros(0)}
     assert all(np.isfinite(a).all() for a in got["params"]) and np.isfinite(got["step_loss"]).all()
     dev_p, dev_l = C.rel_dev(got, ref)
     bar_p, bar_l = max(4 * env_p, FLOOR), max(4 * env_l, FLOOR)
     print(f"{C.train_id(c)}: parameters device {dev_p:.2e} (CPU f32 {env_p:.2e}, bar {bar_p:.2e}); "
           f"losses device {dev_l:.2e} (CPU f32 {env_l:.2e}, bar {bar_l:.2e})")
-    _note("b", "parameters", dev_p, bar_p)
-    _note("b", "losses", dev_l, bar_l)
+    _note("b", "parameters", RG._ratio(dev_p, bar_p))
+    _note("b", "losses", RG._ratio(dev_l, bar_l))
     assert dev_p <= bar_p
     assert dev_l <= bar_l
 
@@ -293,11 +279,11 @@ def test_sentiment_model_forward_and_autograd(gpu, d, h, o, b):
     with torch.no_grad():
         y = m(x.to(gpu))
     assert not y.requires_grad and y.shape == yr.squeeze().shape
-    _check("d", "SentimentModel no-grad", _host(y).reshape(b, o), yr.detach().numpy(), y_bound)
+    _check("d", "SentimentModel no-grad", _host64(y).reshape(b, o), yr.detach().numpy(), y_bound)
     xg = x.to(gpu).requires_grad_(True)
     y = m(xg)
     assert y.requires_grad
-    _check("d", "SentimentModel autograd y", _host(y.detach()).reshape(b, o), yr.detach().numpy(), y_bound)
+    _check("d", "SentimentModel autograd y", _host64(y.detach()).reshape(b, o), yr.detach().numpy(), y_bound)
     y.reshape(b, o).backward(dy.to(gpu))
     hid = np.maximum(pre, 0)
     g, bounds = C.backward_bounds(xn, hid, params[0], params[2], dyn)
@@ -308,7 +294,7 @@ def test_sentiment_model_forward_and_autograd(gpu, d, h, o, b):
             "db2": ref[2].bias.grad}
     for k in got:
         np.testing.assert_allclose(g[k], want[k].numpy(), rtol=0, atol=1e-12)  # the oracle is torch's autograd
-        _check("d", "SentimentModel autograd " + k, _host(got[k]), want[k].numpy(), bounds[k])
+        _check("d", "SentimentModel autograd " + k, _host64(got[k]), want[k].numpy(), bounds[k])
 
 
 def mirror_case(d, seed):
@@ -381,7 +367,7 @@ def test_train_sentiment_for_latents_vs_oracle(gpu, d):
     bar_p, bar_l = max(4 * env_p, FLOOR), max(4 * env_l, FLOOR)
     print(f"d {d}: parameters device {dev_p:.2e} (CPU f32 {env_p:.2e}, bar {bar_p:.2e}); "
           f"losses device {dev_l:.2e} (CPU f32 {env_l:.2e}, bar {bar_l:.2e})")
-    _note("d", "train_sentiment_for_latents parameters", dev_p, bar_p)
-    _note("d", "train_sentiment_for_latents losses", dev_l, bar_l)
+    _note("d", "train_sentiment_for_latents parameters", RG._ratio(dev_p, bar_p))
+    _note("d", "train_sentiment_for_latents losses", RG._ratio(dev_l, bar_l))
     assert dev_p <= bar_p
     assert dev_l <= bar_l

@@ -19,10 +19,12 @@ poisoned, and the case tables.  One assertion shape throughout:
 
 No tolerance is involved: the bar is the same kernel on clean scratch.  One Z
 run per family is also held to the float64 bar of that family's own test
-(through that test's helper), so the baseline is not garbage, and
+(through the family's checker in tests/mmb2_gpu.py, widths_gpu.py,
+regressor_gpu.py or word_cases.py), so the baseline is not garbage, and
 test_control_poison_reaches_the_output shows that both patterns are visible
 through a reduction.  Each family prints one line per case, "<case>: N ok / H
-ok".
+ok"; the module prints at its end, per family and quantity, how many Z runs
+were held to a bar and the largest fraction of it they reached.
 
 Only the product library is loaded.
 """
@@ -31,26 +33,45 @@ import pytest
 import torch
 
 import frames16_cases as F
+import fused_cases as FC
 import latent as LT
 import mmb2_cases as C
+import mmb2_gpu as MG
 import mmb_lib as L
 import models
 import pipeline as P
 import regressor_cases as R
+import regressor_gpu as RG
 import scratch_cases as S
 import synth
-import test_gpu_fused_tail as TF
-import test_gpu_mmb2_widths as TW
-import test_gpu_regressor_widths as TR
-import test_gpu_widths as TD
-import test_gpu_word_widths as TWW
 import width_cases as W
+import widths_gpu as WG
 import word_cases as WC
+from common_gpu import TOL, Ledger, _dev, _dev32, _networks
+from oracle import mmb2_oracle as M
 from oracle import sif_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 U8 = torch.uint8
+
+_WORST = Ledger()  # (family, what) -> [comparisons, largest error as a fraction of its bar]
+
+
+def _note(family, what, value, bar=1.0):
+    """The `note` handed to the families' checkers, (family, what, fraction) or
+    (family, what, error, bar): the Z runs held to their family's float64 bars."""
+    _WORST.note((str(family), what), value / bar)
+    return float(value)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report():
+    yield
+    for (family, what), (n, frac) in sorted(_WORST.items()):
+        print(f"\nscratch, Z run against family {family} {what}: {n} comparisons, largest {frac:.3f} of its bar",
+              end="")
+    print()
 
 
 # ------------------------------------------------------------------ the engine
@@ -59,7 +80,7 @@ def _buf(shape, dtype, pattern, gpu, keep=()):
     return S.poison(torch.empty(shape, dtype=dtype, device=gpu), pattern, keep)
 
 
-def _host(t):
+def _cpu(t):
     return t.detach().contiguous().cpu()
 
 
@@ -116,14 +137,14 @@ def test_control_poison_reaches_the_output(gpu):
 # ------------------------------------------------------------------ 1: Gram
 def _gram_rows(n, d, gpu):
     num32 = W.x32(n, d).astype(np.float32)
-    cnt32 = TD._counts(n, n + d)
-    return num32, cnt32, TD._dev(num32, gpu), TD._dev(cnt32, gpu)
+    cnt32 = WG._counts(n, n + d)
+    return num32, cnt32, _dev(num32, gpu), _dev(cnt32, gpu)
 
 
 def _known_matrix(d, gpu):
     """The matrix an accumulating call adds to (symmetric, f64, exact in f32)."""
     a = np.random.default_rng(d).integers(-8, 9, size=(d, d)).astype(np.float64)
-    return TD._dev(a + a.T, gpu), a + a.T
+    return _dev(a + a.T, gpu), a + a.T
 
 
 def _gram_sweep(label, launch, n, d, gpu, G0=None, ws_rows=None):
@@ -135,7 +156,7 @@ def _gram_sweep(label, launch, n, d, gpu, G0=None, ws_rows=None):
         G = G0.clone() if G0 is not None else _buf((d, d), torch.float64, p, gpu)
         launch(G, G0 is not None, ws)
         _sync()
-        return {"G": _host(G)}
+        return {"G": _cpu(G)}
     return _sweep(label, run)["G"].numpy()
 
 
@@ -145,26 +166,26 @@ def test_gram_f32_rows(gpu, n, d):
     num32, cnt32, num, cnt = _gram_rows(n, d, gpu)
     K0, k0 = _known_matrix(d, gpu)
     for use_cnt in (False, True):
-        X = TD._x_of(num32, cnt32 if use_cnt else None)
+        X = WG._x_of(num32, cnt32 if use_cnt else None)
         exact = X.T @ X
         for acc in (False, True):
             label = f"gram {route} n={n} d={d} cnt={int(use_cnt)} accumulate={int(acc)}"
             G = _gram_sweep(label, lambda G, a, ws: P.gram(num, cnt if use_cnt else None, G, a, ws),
                             n, d, gpu, G0=K0 if acc else None)
-            TD._check_gram(G, exact + k0 if acc else exact, label)  # the family's float64 bar
+            WG._check_gram(_note, G, exact + k0 if acc else exact, label)  # the family's float64 bar
 
 
 @pytest.mark.parametrize("n,d", S.GRAM_F64, ids=lambda v: str(v))
 def test_gram_f64_rows(gpu, n, d):
     X = W.x64(n, d)
-    x = TD._dev(X, gpu)
+    x = _dev(X, gpu)
     K0, k0 = _known_matrix(d, gpu)
     for acc in (False, True):
         def launch(G, a, ws):
             L.call("mmb_gram_f64", L.ptr(x), n, d, L.ptr(G), int(a), L.ptr(ws.buf), L.stream_ptr())
         label = f"gram_f64 n={n} d={d} accumulate={int(acc)}"
         G = _gram_sweep(label, launch, n, d, gpu, G0=K0 if acc else None)
-        TD._check_gram(G, X.T @ X + (k0 if acc else 0.0), label)
+        WG._check_gram(_note, G, X.T @ X + (k0 if acc else 0.0), label)
 
 
 @pytest.mark.parametrize("chunks", S.GRAM_PART_CHUNKS, ids=lambda v: "-".join(map(str, v)))
@@ -177,7 +198,7 @@ def test_gram_two_phase(gpu, chunks):
     num32, cnt32, num, cnt = _gram_rows(n_plan, d, gpu)
     K0, k0 = _known_matrix(d, gpu)
     for use_cnt in (False, True):
-        X = TD._x_of(num32[:rows], cnt32[:rows] if use_cnt else None)
+        X = WG._x_of(num32[:rows], cnt32[:rows] if use_cnt else None)
         for acc in (False, True):
             def launch(G, a, ws):
                 r0 = 0
@@ -189,13 +210,13 @@ def test_gram_two_phase(gpu, chunks):
                 L.call("mmb_gram_finish", n_plan, d, L.ptr(G), int(a), L.ptr(ws.buf), L.stream_ptr())
             label = f"gram two-phase chunks={chunks} cnt={int(use_cnt)} accumulate={int(acc)}"
             G = _gram_sweep(label, launch, n_plan, d, gpu, G0=K0 if acc else None)
-            TD._check_gram(G, X.T @ X + (k0 if acc else 0.0), label)
+            WG._check_gram(_note, G, X.T @ X + (k0 if acc else 0.0), label)
 
 
 @pytest.mark.parametrize("n,d", S.GRAM_I8, ids=lambda v: str(v))
 def test_gram_i8(gpu, n, d):
-    x = TD._i8_rows(n, d)
-    xt = TD._dev(x, gpu)
+    x = WG._i8_rows(n, d)
+    xt = _dev(x, gpu)
     K0, k0 = _known_matrix(d, gpu)
     for acc in (False, True):
         cms = []
@@ -209,7 +230,7 @@ def test_gram_i8(gpu, n, d):
         G = _gram_sweep(label, launch, n, d, gpu, G0=K0 if acc else None)
         assert all(np.array_equal(cm.cpu().numpy().view(np.float32), np.abs(x).max(0)) for cm in cms)
         if not acc and n <= 5000:  # the family's bars (the sliced oracle costs O(n d^2) on the CPU)
-            TD._check_gram_i8(G, x)
+            WG._check_gram_i8(_note, G, x)
 
 
 # ------------------------------------------------------------------ 2: stream kernels, column bounds
@@ -244,11 +265,11 @@ def _stream_sweep(case, gpu, modes=S.STREAM_MODES, kind=None, split_parts=None, 
     D, A, Vd, T, N, V = case
     z = C.inputs(case)
     if kind is None:
-        au, vi = TW._dev(z["audio"], gpu), TW._dev(z["visual"], gpu)
+        au, vi = _dev(z["audio"], gpu), _dev(z["visual"], gpu)
     else:
         au, vi = (t.to(gpu) for t in F.frames(case, kind))
     for mode in modes:
-        kw = TW._text_args(z, mode, gpu)
+        kw = MG._text_args(z, mode, gpu)
         for s_half in (False, True):
             def run(p):
                 out = _stream_outputs(case, s_half, p, gpu)
@@ -261,17 +282,17 @@ def _stream_sweep(case, gpu, modes=S.STREAM_MODES, kind=None, split_parts=None, 
                 num, s, aux = P.mm2_stream(N, T, D, A, Vd, au, vi, s_half=s_half, flag=flag, out=out,
                                            colmax=colmax, colmax_ws=ws, **kw, **extra)
                 _sync()
-                return {"x": _host(num), "s": _host(s), "aux": _host(aux), "colmax": _host(colmax),
-                        "flag": _host(flag)}
+                return {"x": _cpu(num), "s": _cpu(s), "aux": _cpu(aux), "colmax": _cpu(colmax),
+                        "flag": _cpu(flag)}
             label = (f"stream {C.shape_id(case)} {mode} s_half={int(s_half)}"
                      + (f" {kind}" if kind else "") + (f" parts={split_parts}" if split_parts is not None else ""))
             out = _sweep(label, run)
             assert int(out["flag"]) == 0
             _stream_checks(case, s_half, out)
             if anchor:  # the family's float64 bars (tests/test_gpu_mmb2_widths.py)
-                TW._check_stream(11, case,(out["x"].numpy(), out["s"].numpy(), out["aux"].numpy(),
+                MG._check_stream(_note, 11, case, (out["x"].numpy(), out["s"].numpy(), out["aux"].numpy(),
                                                    out["colmax"].numpy().view(np.float32)),
-                                 TW._ref(case, emb2=mode == "dense+emb2"), s_half)
+                                 MG._ref(case, emb2=mode == "dense+emb2"), s_half)
 
 
 @pytest.mark.parametrize("shape,n,family", S.STREAM_CASES,
@@ -309,8 +330,8 @@ def _split_ws(n, kp, slices, p, gpu):
 def test_split_k_projection(gpu, D, A, Vd):
     for N in S.PROJECT_N:
         case = C.case_of((D, A, Vd, S.PROJECT_T), N)
-        num, s32, s16, aux, aux16, proj = TW._operands(case, gpu)
-        pc = TW._dev(W.orthonormal_rows(1, D, seed=D + N), gpu)
+        num, s32, s16, aux, aux16, proj = MG._operands(case, gpu)
+        pc = _dev(W.orthonormal_rows(1, D, seed=D + N), gpu)
         for slices in S.PROJECT_SLICES:
             for with_pc in (False, True):
                 def run(p):
@@ -319,13 +340,13 @@ def test_split_k_projection(gpu, D, A, Vd):
                     P.mm2_project(s16, num, aux16, proj, out=out, pc=pc if with_pc else None, sif_out=sif,
                                   split=_split_ws(N, proj.kp, slices, p, gpu), slices=slices)
                     _sync()
-                    return {"mmb2": _host(out), **({"sif": _host(sif)} if with_pc else {})}
+                    return {"mmb2": _cpu(out), **({"sif": _cpu(sif)} if with_pc else {})}
                 z = _sweep(f"split-K {C.shape_id(case)} slices={slices} pc={int(with_pc)}", run)
                 if case == S.PROJECT_ANCHOR and slices == 2:  # the family's float64 bars
-                    TW._check_rows(7, "split-K projection", case, z["mmb2"], TW._dequant(s16, aux16, proj.kp),
+                    MG._check_rows(_note, 7, "split-K projection", case, z["mmb2"], MG._dequant(s16, aux16, proj.kp),
                                    num, aux16, proj, x3=True)
                     if with_pc:
-                        TW._check_removed(case, z["sif"], num, pc.cpu().numpy(), gpu)
+                        MG._check_removed(_note, case, z["sif"], num, pc.cpu().numpy(), gpu)
 
 
 # ------------------------------------------------------------------ 4: derived images
@@ -355,7 +376,7 @@ def _rebuilt_projection(nets, dims, p, gpu, text=None):
             S.poison(getattr(proj, name), p)
     proj.refresh()
     _sync()
-    img = {name: _host(S._bytes_of(getattr(proj, name))[:sizes[name]]) for name in IMAGES
+    img = {name: _cpu(S._bytes_of(getattr(proj, name))[:sizes[name]]) for name in IMAGES
            if getattr(proj, name, None) is not None}
     return proj, img
 
@@ -383,9 +404,9 @@ def _images_and_consumers(label, nets, dims, N, inp, front, gpu, text=None, anch
                          table=inp["table"], wtab32=inp["wtab"], flag=flag, out=fo, colmax=colmax,
                          colmax_ws=ws)  # the fused kernels read wpieces, c0 (and the text cache)
         _sync()
-        out.update({"project": _host(o32), "project_x3": _host(o16), "fused x": _host(x),
-                    "fused aux": _host(fa), "fused mmb2": _host(m), "fused colmax": _host(colmax),
-                    "flag": _host(flag)})
+        out.update({"project": _cpu(o32), "project_x3": _cpu(o16), "fused x": _cpu(x),
+                    "fused aux": _cpu(fa), "fused mmb2": _cpu(m), "fused colmax": _cpu(colmax),
+                    "flag": _cpu(flag)})
         return out
     z = _sweep(label, run)
     assert int(z["flag"]) == 0
@@ -394,18 +415,18 @@ def _images_and_consumers(label, nets, dims, N, inp, front, gpu, text=None, anch
     assert not wm[K:].any() and not wm[:, D + 1:].any() and not c0[D + 1:].any()  # the K and ldw pads
     if anchor_case is not None:  # the family's float64 bars, on the x3 consumer and the fused rows
         proj = keep["proj"]
-        TW._check_rows(7, "x3 on a rebuilt image", anchor_case, z["project_x3"],
-                       TW._dequant(s16, aux16, proj.kp), num, aux16, proj, x3=True)
-        e = TW.M.row_rel_err(z["fused mmb2"].numpy(), C.oracle_rows(anchor_case))
-        print(f"{label}: fused rows vs the oracle {e:.3e} (bar {TW.TOL})")
-        assert e < TW.TOL
+        MG._check_rows(_note, 7, "x3 on a rebuilt image", anchor_case, z["project_x3"],
+                       MG._dequant(s16, aux16, proj.kp), num, aux16, proj, x3=True)
+        e = M.row_rel_err(z["fused mmb2"].numpy(), C.oracle_rows(anchor_case))
+        print(f"{label}: fused rows vs the oracle {e:.3e} (bar {TOL})")
+        assert e < TOL
 
 
 @pytest.mark.parametrize("row", S.FUSED_TAIL_ROWS)
 def test_projection_images_and_the_fused_kernel(gpu, row):
-    D, A, Vd, T, N, bad = TF.CASES[row]
+    D, A, Vd, T, N, bad = FC.CASES[row]
     assert not bad and P.stream_project_supported(T, D, A, Vd)
-    inp = synth.device_workload(N, T, TF.V, D=D, A=A, Vd=Vd, seed=83, device=gpu)
+    inp = synth.device_workload(N, T, FC.V, D=D, A=A, Vd=Vd, seed=83, device=gpu)
     torch.manual_seed(0)
     gen = models.AudioVisualGeneratorMultimodal(D, A, Vd, norm=None).to(gpu)
     _images_and_consumers(f"images + fused D{D}-A{A}-V{Vd}-T{T}-N{N}", gen.networks(), (D, A, Vd, T), N,
@@ -416,8 +437,8 @@ def test_projection_images_and_the_fused_kernel(gpu, row):
 def test_projection_images_and_the_narrow_fused_kernel(gpu, case):
     D, A, Vd, T, N, V = case
     assert P.narrow_fused_supported(T, D, A, Vd, V)
-    inp = TW._device_inputs(case, gpu)
-    _images_and_consumers(f"images + narrow fused {C.shape_id(case)}", TW._networks(case, gpu),
+    inp = MG._device_inputs(case, gpu)
+    _images_and_consumers(f"images + narrow fused {C.shape_id(case)}", _networks(case, gpu),
                           (D, A, Vd, T), N, inp, P.mm2_stream_project_narrow, gpu,
                           text=(inp["table"], inp["wtab"]), anchor_case=case if N > 1 else None)
 
@@ -425,14 +446,14 @@ def test_projection_images_and_the_narrow_fused_kernel(gpu, case):
 @pytest.mark.parametrize("D", S.WORD_TABLE_D)
 def test_normalised_word_table(gpu, D):
     V = S.WORD_TABLE_V
-    table = TWW._dev(WC.make_inputs(WC.WordCase(D, V, 1, 1, 0))["table"], gpu)
+    table = _dev32(WC.make_inputs(WC.WordCase(D, V, 1, 1, 0))["table"], gpu)
     Dp = L.query("mmb_word_pad", D)
 
     def run(p):
         wn = _buf((V, Dp), torch.float32, p, gpu)
         L.call("mmb_word_normalize", L.ptr(table), V, D, L.ptr(wn), L.stream_ptr())
         _sync()
-        return {"wn": _host(wn)}
+        return {"wn": _cpu(wn)}
     wn = _sweep(f"word table D={D} V={V}", run)["wn"].numpy().astype(np.float64)
     assert Dp > D and not wn[:, D:].any()  # the pad columns
     assert np.abs(np.linalg.norm(wn, axis=1) - 1.0).max() < 1e-6
@@ -448,8 +469,8 @@ SOLVE_CASES = S.solve_cases()
 
 @pytest.mark.parametrize("n,d,npc", SOLVE_CASES, ids=["n{}-d{}-npc{}".format(*c) for c in SOLVE_CASES])
 def test_pc_solve_workspace(gpu, n, d, npc):
-    assert (n, d, npc) in TD.SOLVE_CASES
-    G, z0, tr, Gd, z0d = TD._solver_inputs(n, d, npc, gpu)
+    assert (n, d, npc) in WG.SOLVE_CASES
+    G, z0, tr, Gd, z0d = WG._solver_inputs(n, d, npc, gpu)
     for n_iter in ((7, 0) if npc == 1 else (7,)):  # 7: the squared rounds read G2 from the workspace
         def run(p):
             ws = _solve_ws(d, p, gpu)
@@ -458,19 +479,19 @@ def test_pc_solve_workspace(gpu, n, d, npc):
             P.pc_solve(Gd, z0d, npc, tr, n_iter=n_iter, out=pc, flag=flag, ws=ws)
             _sync()
             assert not bool(ws[:16].any()), "control words left non-zero"
-            return {"pc": _host(pc), "flag": _host(flag)}
+            return {"pc": _cpu(pc), "flag": _cpu(flag)}
         z = _sweep(f"pc_solve n={n} d={d} npc={npc} n_iter={n_iter}", run)
         assert int(z["flag"]) == 0
         if (n, d, npc) == S.SOLVE_ANCHOR:  # the family's float64 bar
             e = np.abs(z["pc"].numpy() - O.pc_from_gram(G, z0, npc, tr, n_iter=n_iter)).max()
-            print(f"anchor: {e:.3e} (bar {TD.SOLVE_BAR[npc]})")
-            assert e < TD.SOLVE_BAR[npc]
+            print(f"anchor: {e:.3e} (bar {W.SOLVE_BAR[npc]})")
+            assert e < W.SOLVE_BAR[npc]
 
 
 @pytest.mark.parametrize("n,d", S.SOLVE_XT, ids=lambda v: str(v))
 def test_pc_solve_xt_workspace(gpu, n, d):
     X = W.make_x(n, d)
-    x, Gd = TD._dev(X.astype(np.float32), gpu), TD._dev(X.T @ X, gpu)
+    x, Gd = _dev(X.astype(np.float32), gpu), _dev(X.T @ X, gpu)
     k = min(1 + P.N_OVERSAMPLES, d)
     om = P.omega(n, k, gpu)
 
@@ -482,22 +503,22 @@ def test_pc_solve_xt_workspace(gpu, n, d):
                L.ptr(ws), L.ptr(flag), L.stream_ptr())
         _sync()
         assert not bool(ws[:16].any()), "control words left non-zero"
-        return {"pc": _host(pc), "flag": _host(flag)}
+        return {"pc": _cpu(pc), "flag": _cpu(flag)}
     z = _sweep(f"pc_solve_mc_xt n={n} d={d}", run)
     assert int(z["flag"]) == 0
     if W.full_rank(n, d, 1):  # the family's float64 bar
         ref = O.pc_from_gram(X.T @ X, X.T @ om.cpu().numpy(), 1, True)
-        assert np.abs(z["pc"].numpy() - ref).max() < TD.SOLVE_BAR[1]
+        assert np.abs(z["pc"].numpy() - ref).max() < W.SOLVE_BAR[1]
 
 
 # ------------------------------------------------------------------ 6: word likelihood
 def _word_inputs(c, dense, gpu):
     z, lp_ref, g_ref = WC.reference(c, dense)
-    wt = LT.WordTable(TWW._dev(z["table"], gpu))
-    d = {"lat": TWW._dev(z["lat"], gpu), "w": TWW._dev(z["w"], gpu), "mask": TWW._dev(z["mask"], gpu),
-         "up": TWW._dev(z["up"], gpu), "wt": wt,
-         "ids": None if dense else TWW._dev(z["ids"], gpu, torch.int32),
-         "sent": TWW._dev(z["dense"], gpu) if dense else None}
+    wt = LT.WordTable(_dev32(z["table"], gpu))
+    d = {"lat": _dev32(z["lat"], gpu), "w": _dev32(z["w"], gpu), "mask": _dev32(z["mask"], gpu),
+         "up": _dev32(z["up"], gpu), "wt": wt,
+         "ids": None if dense else _dev32(z["ids"], gpu, torch.int32),
+         "sent": _dev32(z["dense"], gpu) if dense else None}
     return d, lp_ref, g_ref
 
 
@@ -518,8 +539,8 @@ def _word_run(c, d, p, gpu, ws=None):
            L.ptr(d["sent"]), c.L, L.ptr(d["w"]), L.ptr(d["mask"]), WC.A, L.ptr(state), L.ptr(gsum),
            L.ptr(cosv), L.ptr(d["up"]), L.ptr(dlat), L.stream_ptr())
     _sync()
-    return {"lp": _host(lp), "state": _host(state), "gsum": _host(gsum), "cos": _host(cosv),
-            "dlat": _host(dlat)}
+    return {"lp": _cpu(lp), "state": _cpu(state), "gsum": _cpu(gsum), "cos": _cpu(cosv),
+            "dlat": _cpu(dlat)}
 
 
 @pytest.mark.parametrize("dense", [False, True], ids=["ids", "dense"])
@@ -529,8 +550,8 @@ def test_word_likelihood(gpu, c, dense):
     z = _sweep(f"word {WC.word_id(c)} {'dense' if dense else 'ids'}", lambda p: _word_run(c, d, p, gpu))
     assert not z["gsum"].numpy()[:, c.D:].any()  # the pad columns of the G sums
     # the family's float64 bars (tests/test_gpu_word_widths.py)
-    assert TWW.lp_ratio(z["lp"].numpy(), lp_ref) <= 1.0
-    assert TWW.grad_ratio(z["dlat"].numpy(), g_ref) <= 1.0
+    assert WC.lp_ratio(z["lp"].numpy(), lp_ref) <= 1.0
+    assert WC.grad_ratio(z["dlat"].numpy(), g_ref) <= 1.0
 
 
 # ------------------------------------------------------------------ 7: regressor
@@ -541,8 +562,8 @@ def test_mlp_backward_workspace(gpu, c, want):
     hid32 = R.f32(z["hid"])
     w1, _, w2, _ = z["params"]
     g, bounds = R.backward_bounds(z["x"], hid32, w1, w2, z["dy"])
-    x, hid, dy = TR._dev(z["x"], gpu), TR._dev(hid32, gpu), TR._dev(z["dy"], gpu)
-    w1d, w2d = TR._dev(w1, gpu), TR._dev(w2, gpu)
+    x, hid, dy = RG._dev(z["x"], gpu), RG._dev(hid32, gpu), RG._dev(z["dy"], gpu)
+    w1d, w2d = RG._dev(w1, gpu), RG._dev(w2, gpu)
     names = ("dh", "dx", "dw1", "db1", "dw2", "db2")
     skip = {"all": (), "no_dx": ("dx",), "no_params": ("dw1", "db1", "dw2", "db2")}[want]
 
@@ -551,17 +572,17 @@ def test_mlp_backward_workspace(gpu, c, want):
         L.call("mmb_mlp_backward", L.ptr(x), L.ptr(hid), c.b, c.d, c.h, c.o, L.ptr(w1d), L.ptr(w2d),
                L.ptr(dy), *[L.ptr(out[k]) for k in names], L.stream_ptr())
         _sync()
-        return {k: _host(t) for k, t in out.items() if t is not None}
+        return {k: _cpu(t) for k, t in out.items() if t is not None}
     zr = _sweep(f"mlp_backward {R.fwd_id(c)} {want}", run)
     for k, t in zr.items():  # the family's float64 bars (tests/test_gpu_regressor_widths.py)
-        TR._check("a", "mmb_mlp_backward " + k, TR._host(t), g[k], bounds[k])
+        RG._check(_note, "a", "mmb_mlp_backward " + k, RG._host64(t), g[k], bounds[k])
 
 
 def _train_outputs(run):
     rc, params, sl, vl, flag = run
     assert rc == 0 and int(flag.item()) == 0
-    return {**{f"p{i}": _host(t) for i, t in enumerate(params)}, "step_loss": _host(sl),
-            **({"valid_loss": _host(vl)} if vl is not None else {})}
+    return {**{f"p{i}": _cpu(t) for i, t in enumerate(params)}, "step_loss": _cpu(sl),
+            **({"valid_loss": _cpu(vl)} if vl is not None else {})}
 
 
 def test_mlp_train_leaves_its_workspace_zero(gpu):
@@ -569,15 +590,15 @@ def test_mlp_train_leaves_its_workspace_zero(gpu):
     on it).  A completed launch leaves ALL of it zero, and a smaller case run
     next on the same workspace equals its run on a fresh zeroed one."""
     small = S.TRAIN_SMALLER
-    fresh = _train_outputs(TR._launch_train(gpu, small, R.make_train_inputs(small),
-                                            TR._workspace(gpu, small.d, small.h)))
+    fresh = _train_outputs(RG._launch_train(gpu, small, R.make_train_inputs(small),
+                                            RG._workspace(gpu, small.d, small.h)))
     for c in S.TRAIN_CASES:
-        ws = TR._workspace(gpu, c.d, c.h)
+        ws = RG._workspace(gpu, c.d, c.h)
         assert ws.numel() * 4 >= L.query("mmb_mlp_workspace_bytes", small.d, small.h)
-        _train_outputs(TR._launch_train(gpu, c, R.make_train_inputs(c), ws))
+        _train_outputs(RG._launch_train(gpu, c, R.make_train_inputs(c), ws))
         left = int(torch.count_nonzero(ws))
         assert left == 0, f"{R.train_id(c)}: {left} of {ws.numel()} workspace words left non-zero"
-        again = _train_outputs(TR._launch_train(gpu, small, R.make_train_inputs(small), ws))
+        again = _train_outputs(RG._launch_train(gpu, small, R.make_train_inputs(small), ws))
         _assert_same(f"mlp_train {R.train_id(small)} after {R.train_id(c)}", "reused workspace", fresh, again)
         assert not ws.any().item()
         print(f"mlp_train {R.train_id(c)}: workspace zero after the launch; {R.train_id(small)} on it "
@@ -619,7 +640,7 @@ def test_reuse_gram_workspace(gpu):
             G = _buf((d, d), torch.float64, p, gpu)
             P.gram(num, cnt, G, False, holder)
             _sync()
-            return {"G": _host(G)}
+            return {"G": _cpu(G)}
         return f"({n}, {d})", run
     _reuse("gram", [make(n, d) for n, d in shapes], gpu)
 
@@ -631,8 +652,8 @@ def test_reuse_split_stream_workspace(gpu):
     def make(case, parts):
         D, A, Vd, T, N, V = case
         z = C.inputs(case)
-        au, vi = TW._dev(z["audio"], gpu), TW._dev(z["visual"], gpu)
-        kw = TW._text_args(z, "ids+table", gpu)
+        au, vi = _dev(z["audio"], gpu), _dev(z["visual"], gpu)
+        kw = MG._text_args(z, "ids+table", gpu)
 
         def run(shared, p):
             if shared is None:
@@ -644,20 +665,20 @@ def test_reuse_split_stream_workspace(gpu):
             out = _stream_outputs(case, True, p, gpu)
             num, s, aux = P.mm2_stream(N, T, D, A, Vd, au, vi, s_half=True, out=out, split=ws, parts=parts, **kw)
             _sync()
-            return {"x": _host(num), "s": _host(s), "aux": _host(aux)}
+            return {"x": _cpu(num), "s": _cpu(s), "aux": _cpu(aux)}
         return f"{C.shape_id(case)} parts={parts}", run
     _reuse("split stream", [make(c, q) for c, q in cases], gpu)
 
 
 def test_reuse_split_k_workspace(gpu):
     cases = [(C.case_of((316, 300, 300, S.PROJECT_T), 300), 7), (C.case_of((256, 8, 12, S.PROJECT_T), 2), 2)]
-    ops = {c: TW._operands(c, gpu) for c, _ in cases}
+    ops = {c: MG._operands(c, gpu) for c, _ in cases}
     nbytes = max(int(L.query("mmb_mm2_project_x3_split_ws_bytes", c[4], ops[c][5].kp, q)) for c, q in cases)
 
     def make(case, slices):
         num, s32, s16, aux, aux16, proj = ops[case]
         N, D = case[4], case[0]
-        pc = TW._dev(W.orthonormal_rows(1, D, seed=D + N), gpu)
+        pc = _dev(W.orthonormal_rows(1, D, seed=D + N), gpu)
 
         def run(shared, p):
             if shared is None:
@@ -669,7 +690,7 @@ def test_reuse_split_k_workspace(gpu):
             out, sif = _buf((N, D), torch.float32, p, gpu), _buf((N, D), torch.float32, p, gpu)
             P.mm2_project(s16, num, aux16, proj, out=out, pc=pc, sif_out=sif, split=ws, slices=slices)
             _sync()
-            return {"mmb2": _host(out), "sif": _host(sif)}
+            return {"mmb2": _cpu(out), "sif": _cpu(sif)}
         return f"{C.shape_id(case)} slices={slices}", run
     _reuse("split-K projection", [make(c, q) for c, q in cases], gpu)
 
@@ -695,7 +716,7 @@ def test_reuse_word_workspace(gpu):
 # ------------------------------------------------------------------ 9: the whole step
 def _make_step(name, gpu):
     case, kw, want = S.STEPS[name]
-    step = P.FusedStep(TW._device_inputs(case, gpu), TW._networks(case, gpu), **kw)
+    step = P.FusedStep(MG._device_inputs(case, gpu), _networks(case, gpu), **kw)
     for k, v in want.items():
         assert getattr(step.plan, k) == v, (name, step.plan)
     if want.get("project") == "fork":
@@ -724,8 +745,8 @@ def _fill_step(step, p):
 
 def _step_outputs(step, sif, mmb2):
     _sync()
-    return {"sif": _host(sif), "mmb2": _host(mmb2), "pc": _host(step.pc), "x": _host(step.x),
-            "flag": _host(step.flag)}
+    return {"sif": _cpu(sif), "mmb2": _cpu(mmb2), "pc": _cpu(step.pc), "x": _cpu(step.x),
+            "flag": _cpu(step.flag)}
 
 
 @pytest.mark.parametrize("name", list(S.STEPS))
@@ -734,7 +755,7 @@ def test_whole_step(gpu, name):
     sif, mmb2 = step.run(check=True)
     ref = _step_outputs(step, sif, mmb2)
     if name == "fused":  # the family's float64 bars (tests/test_gpu_mmb2_widths.py)
-        TW._check_step(case, step, sif, mmb2)
+        MG._check_step(_note, case, step, sif, mmb2)
     for p in S.POISONS:
         filled = _fill_step(step, p)
         sif, mmb2 = step.run(check=True)

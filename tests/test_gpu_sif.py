@@ -14,11 +14,11 @@ import sif_functions as SF
 import synth
 from oracle import mmb2_oracle as M
 from oracle import sif_oracle as O
+from width_cases import EMB_TOL
 
 pytestmark = pytest.mark.gpu
 
 SIF_CASES = ["g1_pom_valid", "g1_pom_test", "g2_mosi", "g3_gap"]
-EMB_TOL = 1e-5
 
 
 def regen_table(z):

@@ -47,21 +47,18 @@ import pipeline as P
 import spectrum_cases as S
 import synth
 import width_cases as W
+from common_gpu import Ledger, _dev
 from oracle import sif_oracle as O
+from width_cases import F32_ROW
+from widths_gpu import _pc_solve_checked, _pc_solve_direct
 
 pytestmark = pytest.mark.gpu
 
-F32_ROW = 2.0 ** -23
-
-_WORST = {}  # (group, what) -> [comparisons, largest error / bar, where]
+_WORST = Ledger()  # (group, what) -> [comparisons, largest error / bar, where]
 
 
 def _note(group, what, err, bar, where):
-    w = _WORST.setdefault((group, what), [0, 0.0, ""])
-    w[0] += 1
-    frac = float(err) / bar
-    if frac >= w[1]:
-        w[1], w[2] = frac, where
+    _WORST.note((group, what), float(err) / bar, where)
     return float(err)
 
 
@@ -72,33 +69,6 @@ def _report():
         print(f"\nspectrum group {group} {what}: {cases} comparisons, largest {frac:.3f} of its bar"
               f" at {where}", end="")
     print()
-
-
-def _dev(a, gpu, dtype=None):
-    t = torch.as_tensor(np.array(a, order="C"))  # (a copy: the cases' arrays are read-only)
-    return (t if dtype is None else t.to(dtype)).to(gpu)
-
-
-def _pc_solve_direct(Gd, z0d, npc, tr, n_iter=P.N_ITER):
-    """mmb_pc_solve itself: pc_solve16_kernel (d <= 320) or pc_solve_kernel."""
-    d, k = Gd.shape[0], z0d.shape[1]
-    pc = torch.full((npc, d), float("nan"), dtype=torch.float64, device=Gd.device)
-    L.call("mmb_pc_solve", L.ptr(Gd), d, L.ptr(z0d), k, npc, n_iter, int(tr), L.ptr(pc),
-           L.stream_ptr())
-    return pc.cpu().numpy()
-
-
-def _pc_solve_checked(Gd, z0d, npc, tr, n_iter=P.N_ITER):
-    """P.pc_solve with a flag and a zeroed workspace of the test's own: the flag
-    stays 0 and the multi-workgroup solver leaves its control words zero."""
-    d = Gd.shape[0]
-    flag = torch.zeros(1, dtype=torch.int32, device=Gd.device)
-    ws = (torch.zeros(L.query("mmb_pc_solve_mc_ws_bytes", d), dtype=torch.uint8, device=Gd.device)
-          if d <= P.PC_SOLVE_MC_MAX_D else None)
-    pc = P.pc_solve(Gd, z0d, npc, tr, n_iter=n_iter, flag=flag, ws=ws).cpu().numpy()
-    assert int(flag.item()) == 0
-    assert ws is None or not bool(ws[:16].any())
-    return pc
 
 
 def _hold(group, what, pc, ref, bars, case, alt=None, i8=False):

@@ -24,31 +24,11 @@ import mmb_lib as L
 import models
 import pipeline as P
 import synth
+from mmb2_gpu import _pom
 from oracle import mmb2_oracle as M
 from oracle import sif_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-
-def _pom(golden, case, n, A, Vd, seed, dev):
-    """The reference's own POM split ids (pom_valid_ids 100 x 1089 /
-    pom_test_ids 203 x 1357, g11) and weights, the seeded V = 7763 table,
-    word-aligned frames set to -10 past each transcript's last token."""
-    z = golden("g11_pom_splits")
-    ids = z[f"{case}_ids"][:n]
-    N, T = ids.shape
-    E = synth.word_table(len(z["weights"]), 300, seed=int(z["table_seed"]))
-    last = np.where(ids != 0, np.arange(T)[None, :], -1).max(1)
-    pad = np.arange(T)[None, :] > last[:, None]
-    audio = synth.frames(N, T, A, seed=seed)
-    visual = synth.frames(N, T, Vd, seed=seed + 1)
-    audio[pad] = -10.0
-    visual[pad] = -10.0
-    inp = {"table": torch.tensor(E, device=dev),
-           "wtab": torch.tensor(z["weights"], device=dev, dtype=torch.float32),
-           "ids": torch.as_tensor(ids, dtype=torch.int32, device=dev),
-           "audio": torch.tensor(audio, device=dev), "visual": torch.tensor(visual, device=dev)}
-    return inp, (E, z["weights"], ids, audio, visual)
 
 
 def _stream(inp, s_half, split=None, parts=0, dense=False, colmax=False):

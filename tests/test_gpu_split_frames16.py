@@ -36,9 +36,9 @@ import pipeline as P
 import split_frames16_cases as SF
 import synth
 from frames16_gpu import _dev, _i32
+from mmb2_gpu import _pom
 from oracle import mmb2_oracle as M
 from oracle import sif_oracle as O
-from test_gpu_split import _pom
 
 pytestmark = pytest.mark.gpu
 

@@ -30,8 +30,9 @@ import mmb2_cases as C
 import mmb_lib as L
 import pipeline as P
 import table16_cases as T
-from frames16_gpu import (F32_ROW, TOL, _assert_graph_replays, _bufs, _colmax_bufs, _dev, _networks, _off, _run,
-                          _untouched)
+from frames16_gpu import (F32_ROW, TOL, TWIN, _assert_graph_replays, _bufs, _colmax_bufs, _dev, _frames_of, _networks,
+                          _off, _run, _untouched)
+from mmb2_gpu import _is_narrow_route
 from oracle import mmb2_oracle as M
 from oracle import sif_oracle as O
 
@@ -39,12 +40,6 @@ pytestmark = pytest.mark.gpu
 
 MODES = ("ids+table", "ids+w")
 KIND_IDS = list(T.KINDS)
-
-
-def _is_narrow_route(case, mode, s_half):
-    D, A, Vd, T_, N, V = case
-    return (mode == "ids+table" and s_half and 256 < D <= 512 and max(A, Vd) <= 128 and T_ <= 64
-            and D % 4 == A % 4 == Vd % 4 == 0)
 
 
 class _Launcher:
@@ -85,14 +80,6 @@ def _equal(got, twin, what, names=("x", "s", "aux", "colmax")):
         assert np.array_equal(g, t), (what, name)
         # ... and on the bits, so that +0 / -0 count as different
         assert np.array_equal(_bits(g), _bits(t)), (what, name, "bits")
-
-
-def _frames_of(case, kind, frames, gpu):
-    """The case's frames on the device: f32, or rounded to the table's kind."""
-    if frames == "f32":
-        z = C.inputs(case)
-        return _dev(z["audio"], gpu), _dev(z["visual"], gpu)
-    return tuple(_dev(t, gpu) for t in F.frames(case, kind))
 
 
 def _sweep(case, gpu, table16=T.table, off16=0, off32=0):
@@ -317,7 +304,6 @@ def test_fused_mirrors_and_the_text_cache_reject_a_non_f32_table(gpu):
 
 
 # ------------------------------------------------------------------ D: the step
-TWIN = dict(stream_project=False, narrow_fused=False, split_stream=False)
 EVERYTHING = dict(stream_project=True, narrow_fused=True, split_stream=True, fused_frames16=True,
                   narrow_frames16=True, split_frames16=True)
 

@@ -46,24 +46,21 @@ import sif
 import sif_functions as SF
 import synth
 import width_cases as W
+import widths_gpu as WG
+from common_gpu import Ledger, _dev, _off
 from oracle import mmb2_oracle as M
 from oracle import sif_oracle as O
+from width_cases import EMB_TOL, F32_ROW, PC_BAR, SOLVE_BAR
+from widths_gpu import (SOLVE_CASES, _counts, _i8_rows, _pc_solve_checked, _pc_solve_direct, _solver_inputs,
+                        _x_of)
 
 pytestmark = pytest.mark.gpu
 
-EMB_TOL = 1e-5
-F32_ROW = 2.0 ** -23  # one f32 rounding (2^-24 of the element) with 2x margin, of the row's max
-PC_BAR = {1: 1e-10, 2: 1e-10, 6: 1e-8}
-SOLVE_BAR = {1: 1e-12, 2: 1e-10}
-
-_WORST = {}  # (group, what) -> [cases, largest error, bar]
+_WORST = Ledger()  # (group, what) -> [cases, largest error, bar]
 
 
 def _note(group, what, err, bar):
-    w = _WORST.setdefault((group, what), [0, 0.0, bar])
-    w[0] += 1
-    w[1] = max(w[1], float(err))
-    return float(err)
+    return _WORST.note((group, what), err, bar)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -75,31 +72,9 @@ def _report():
     print()
 
 
-def _dev(a, gpu, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).to(gpu)
-
-
 def _off4(t):
-    """A contiguous copy of f32 `t` that starts 4 bytes past a 16-byte boundary
-    (a slice of a flat buffer)."""
-    flat = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    out = flat[1:].view(t.shape)
-    out.copy_(t)
-    assert out.is_contiguous() and out.data_ptr() % 16 == 4
-    return out
-
-
-def _counts(n, seed):
-    """Positive per-row counts as f32 (count_nonzero(w) of sif_functions.py:55)."""
-    return np.random.default_rng(seed).integers(1, 8, size=n).astype(np.float32)
-
-
-def _x_of(num32, cnt32):
-    """X = f32(num) / f32(cnt), the f32 division the kernels do, widened."""
-    if cnt32 is None:
-        return num32.astype(np.float64)
-    return (num32 / cnt32[:, None]).astype(np.float32).astype(np.float64)
+    """A contiguous copy of f32 `t` that starts 4 bytes past a 16-byte boundary."""
+    return _off(t, 1)
 
 
 # ------------------------------------------------------------------ 1: drop-ins over the table
@@ -151,16 +126,6 @@ def test_dropins_reject_d513_and_npc7(gpu):
 
 
 # ------------------------------------------------------------------ 2: the Gram alone
-def _check_gram(G, ref, what):
-    """G (device or numpy) is symmetric and within 1e-13 of max |G| of the
-    exact f64 Gram `ref`; returns the error."""
-    G = G.cpu().numpy() if isinstance(G, torch.Tensor) else G
-    assert np.array_equal(G, G.T), what
-    e = _note(2, "Gram", np.abs(G - ref).max() / np.abs(ref).max(), 1e-13)
-    assert e < 1e-13, (what, e)
-    return e
-
-
 @pytest.mark.parametrize("n,d", W.SHAPES, ids=[W.shape_id(s) for s in W.SHAPES])
 def test_gram_routes(gpu, n, d):
     num32 = W.x32(n, d).astype(np.float32)
@@ -170,7 +135,7 @@ def test_gram_routes(gpu, n, d):
 
     def check(G, ref, what):
         nonlocal worst
-        worst = max(worst, _check_gram(G, ref, what))
+        worst = max(worst, WG._check_gram(_note, G, ref, what))
 
     X = _x_of(num32, None)
     exact = X.T @ X
@@ -187,26 +152,6 @@ def test_gram_routes(gpu, n, d):
 
 
 # ------------------------------------------------------------------ 3: the int8 Gram
-def _i8_rows(n, d):
-    """Heavy-tailed t(3) rows with one all-zero column (f32)."""
-    rng = np.random.default_rng(1000 * n + d)
-    x = rng.standard_t(3, size=(n, d)).astype(np.float32)
-    x[:, d // 2] = 0.0
-    return x
-
-
-def _check_gram_i8(G, x):
-    """The int8 Gram G (numpy) of the f32 rows x: symmetric, 1e-13 against the
-    sliced oracle, 2e-9 against the exact f64 Gram."""
-    ref = O.sliced_gram(x)
-    exact = x.astype(np.float64).T @ x.astype(np.float64)
-    e1 = _note(3, "vs sliced oracle", np.abs(G - ref).max() / np.abs(ref).max(), 1e-13)
-    e2 = _note(3, "vs exact", np.abs(G - exact).max() / np.abs(exact).max(), 2e-9)
-    print(f"int8 Gram vs sliced oracle {e1:.3e} (bar 1e-13), vs exact {e2:.3e} (bar 2e-9)")
-    assert e1 <= 1e-13 and e2 <= 2e-9
-    assert np.array_equal(G, G.T)
-
-
 @pytest.mark.parametrize("n", [7, 320, 5000])
 @pytest.mark.parametrize("d", [4, 12, 20, 64, 260, 304])
 def test_gram_i8_widths(gpu, n, d):
@@ -214,7 +159,7 @@ def test_gram_i8_widths(gpu, n, d):
     xt = _dev(x, gpu)
     cm = P.colmax(xt)
     assert np.array_equal(cm.cpu().numpy().view(np.float32), np.abs(x).max(0))
-    _check_gram_i8(P.gram_i8(xt, cm).cpu().numpy(), x)
+    WG._check_gram_i8(_note, P.gram_i8(xt, cm).cpu().numpy(), x)
 
 
 @pytest.mark.parametrize("d", [308, 302])
@@ -254,38 +199,6 @@ def test_xt_omega_transposed_shapes(gpu, n, d):
 
 
 # ------------------------------------------------------------------ 5: the solvers from G, z0
-def _solver_inputs(n, d, npc, gpu):
-    X = W.x32(n, d)
-    G = X.T @ X
-    z0, tr = W.start_block(X, npc)
-    return G, z0, tr, _dev(G, gpu), _dev(z0, gpu)
-
-
-def _pc_solve_direct(Gd, z0d, npc, tr, n_iter=P.N_ITER):
-    """mmb_pc_solve itself: pc_solve16_kernel (d <= 320) or pc_solve_kernel."""
-    d, k = Gd.shape[0], z0d.shape[1]
-    pc = torch.full((npc, d), float("nan"), dtype=torch.float64, device=Gd.device)
-    L.call("mmb_pc_solve", L.ptr(Gd), d, L.ptr(z0d), k, npc, n_iter, int(tr), L.ptr(pc),
-           L.stream_ptr())
-    return pc.cpu().numpy()
-
-
-def _pc_solve_checked(Gd, z0d, npc, tr, n_iter=P.N_ITER):
-    """P.pc_solve with a flag and a workspace of the test's own: the flag stays
-    0 and the multi-workgroup solver leaves its control words zero."""
-    d = Gd.shape[0]
-    flag = torch.zeros(1, dtype=torch.int32, device=Gd.device)
-    ws = (torch.zeros(L.query("mmb_pc_solve_mc_ws_bytes", d), dtype=torch.uint8, device=Gd.device)
-          if d <= P.PC_SOLVE_MC_MAX_D else None)
-    pc = P.pc_solve(Gd, z0d, npc, tr, n_iter=n_iter, flag=flag, ws=ws).cpu().numpy()
-    assert int(flag.item()) == 0
-    assert ws is None or not bool(ws[:16].any())
-    return pc
-
-
-SOLVE_CASES = [(n, d, npc) for n, d, npc in W.pc_cases() if npc in SOLVE_BAR]
-
-
 @pytest.mark.parametrize("n,d,npc", SOLVE_CASES, ids=["n{}-d{}-npc{}".format(*c) for c in SOLVE_CASES])
 def test_solvers_from_gram(gpu, n, d, npc):
     G, z0, tr, Gd, z0d = _solver_inputs(n, d, npc, gpu)

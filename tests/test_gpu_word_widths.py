@@ -30,17 +30,14 @@ import torch
 import latent as LT
 import mmb_lib as L
 import word_cases as W
+from common_gpu import Ledger
+from common_gpu import _dev32 as _dev  # float32 unless told otherwise
+from word_cases import grad_ratio, lp_ratio
 
 pytestmark = pytest.mark.gpu
 
-_WORST = {}
-
-
-def _note(what, ratio):
-    w = _WORST.setdefault(what, [0, 0.0])
-    w[0] += 1
-    w[1] = max(w[1], float(ratio))
-    return float(ratio)
+_WORST = Ledger()
+_note = _WORST.note  # (what, ratio)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -49,22 +46,6 @@ def _report():
     for what, (n, r) in sorted(_WORST.items()):
         print(f"\nword widths {what}: {n} comparisons, largest {r:.3f} of its bar", end="")
     print()
-
-
-def _dev(a, gpu, dtype=torch.float32):
-    return torch.as_tensor(np.array(a)).to(dtype).to(gpu).contiguous()  # (a copy: the cached inputs are read-only)
-
-
-def lp_ratio(y, ref, rtol=2e-5, atol=1e-4):
-    y, ref = np.asarray(y, np.float64), np.asarray(ref, np.float64)
-    assert y.shape == ref.shape
-    return float((np.abs(y - ref) / (rtol * np.abs(ref) + atol)).max())
-
-
-def grad_ratio(g, ref, tol=2e-4):
-    g, ref = np.asarray(g, np.float64), np.asarray(ref, np.float64)
-    assert g.shape == ref.shape
-    return float((np.abs(g - ref).max(1) / (tol * np.abs(ref).max(1))).max())
 
 
 @pytest.mark.parametrize("dense", [False, True], ids=["ids", "dense"])

@@ -333,8 +333,10 @@ def test_remove_reference_a_second_way(name):
 
 
 def test_removal_bar_is_the_suite_s():
-    src = open(__file__.replace("test_large_cases.py", "test_gpu_widths.py")).read()
-    assert "F32_ROW = 2.0 ** -23" in src and LC.F32_ROW == 2.0 ** -23
+    """One definition, with the width tables; large_cases and the GPU tests import it."""
+    assert LC.F32_ROW is W.F32_ROW and W.F32_ROW == 2.0 ** -23
+    src = open(__file__.replace("test_large_cases.py", "large_cases.py")).read()
+    assert "F32_ROW =" not in src
 
 
 def test_projection_reference_and_family_conditions():

@@ -11,15 +11,7 @@ import numpy as np
 import pytest
 
 import mmb_lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mmb.h")
-
-
-def declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(mmb_[a-z0-9_]+)\s*\(", src)))
+from abi_cases import ENTRY_ARGS, ROOT, declared_functions
 
 
 def test_header_declares_entry_points():
@@ -146,32 +138,6 @@ def test_invalid_arguments_rejected_without_gpu():
 P = 0x7F0000001000
 KCMAX_ROWS = 8192  # rows of the column-bound workspace (mmb_mm2_colmax_ws_bytes(d) // (4 d))
 
-STREAM = ("ids table v wtab32 text_dense emb_dense w_dense audio visual n t d a vd num_out s_out "
-          "s_half aux_out flag colmax colmax_ws").split()
-ENTRY_ARGS = {
-    "mmb_sif_wavg": "table v d ids n l w wtab32 x_out num_out cnt_out flag stream".split(),
-    "mmb_mm2_stream": STREAM + ["stream"],
-    "mmb_mm2_stream_split": STREAM + "parts ws ws_bytes stream".split(),
-    "mmb_mm2_stream_project": ("ids table v wtab32 text_dense w_dense audio visual n t d a vd wpieces c0 "
-                               "num_out aux_out mmb2_out flag colmax colmax_ws stream").split(),
-    "mmb_mm2_stream_project_narrow": ("ids table v wtab32 text_cache audio visual n t d a vd wpieces c0 "
-                                      "num_out aux_out mmb2_out flag colmax colmax_ws stream").split(),
-    "mmb_mm2_project_x3": "s_split num aux wsplit ldw c0 n k d out stream".split(),
-    "mmb_mm2_project_x3_rmpc": "s_split num aux wsplit ldw c0 n k d out pc sif_out stream".split(),
-    "mmb_mm2_project_x3_split": ("s_split num aux wsplit ldw c0 n k d out pc sif_out slices ws ws_bytes "
-                                 "stream").split(),
-    "mmb_layer_norm_backward": "dy x mean rstd gamma n d dx dgamma dbeta stream".split(),
-    "mmb_mm2_project": "s num aux wm ldw c0 n k d out stream".split(),
-    "mmb_colmax": "x n d colmax accumulate stream".split(),
-    "mmb_mlp_forward": "latents idx b d h o w1 b1 w2 b2 y_out stream".split(),
-    "mmb_mlp_eval": "latents labels perm n batch d h o w1 b1 w2 b2 batch_loss pred_out stream".split(),
-    "mmb_mlp_forward_train": "x b d h o w1 b1 w2 b2 y_out hid_out stream".split(),
-    "mmb_mlp_backward": "x hid b d h o w1 w2 dy dh_ws dx dw1 db1 dw2 db2 stream".split(),
-    "mmb_word_logprob_forward": ("latents b d wn v ids table sent_dense l w mask a want_grad ws lp state gsum "
-                                 "cos_out stream").split(),
-    "mmb_word_logprob_backward": ("latents b d v ids table sent_dense l w mask a state gsum cosv dlp dlat "
-                                  "stream").split(),
-}
 # a valid gathered-text call of each kind (n > 0: it would go on to launch)
 GATHER = dict(ids=P, table=P, v=1000, wtab32=P, text_dense=None, emb_dense=None, w_dense=None, audio=P,
               visual=P, n=100, t=40, d=300, a=300, vd=300, num_out=P, s_out=P, s_half=1, aux_out=P,

@@ -12,11 +12,11 @@ import inspect
 
 import pytest
 
+import abi_cases as ABI
 import frames16_cases as F
 import mmb_lib
 import narrow_frames16_cases as NF
-import test_frames16_cases as T16
-import test_lib_abi as ABI
+
 
 KINDS = list(NF.KINDS)
 NAME = "mmb_mm2_stream_project_narrow_ft"
@@ -80,13 +80,13 @@ def test_stream_project_narrow_ft_argument_table_without_gpu(what, change, want)
 def _plan(name):
     import pipeline as PL
 
-    shape = T16._shapes()[name]
+    shape = F._shapes()[name]
     shape = {"n_total": shape["n"], **shape}
     return lambda **kw: PL.step_plan(d=300, npc=1, cus=256, **shape, **kw)
 
 
 def test_the_mosi_plan_shape_is_the_issue_s():
-    s = T16._shapes()["mosi"]
+    s = F._shapes()["mosi"]
     assert (s["a"], s["vd"], s["t"], s["V"]) == (76, 48, 20, 3016)
 
 
@@ -143,7 +143,7 @@ def test_keyword_on_past_the_text_cache(kind):
     """V > 16384 at MOSI's widths: unsupported, quietly the stream kernel."""
     import pipeline as PL
 
-    shape = dict(T16._shapes()["mosi"])
+    shape = dict(F._shapes()["mosi"])
     shape = {"n_total": shape["n"], **shape, "V": 16385}
     plan = lambda **kw: PL.step_plan(d=300, npc=1, cus=256, **shape, **kw)  # noqa: E731
     assert plan().front == "stream"

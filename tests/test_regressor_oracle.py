@@ -8,7 +8,6 @@ decay at epochs 100 and 200, then the early stop at epoch 300,
 sentiment_model.py:132-160) -- bit for bit: the oracle is the reference's
 loop in the same torch CPU arithmetic.
 """
-import importlib.util
 import json
 import os
 
@@ -19,28 +18,7 @@ import torch
 from conftest import GOLDEN
 from losses import full_loss
 from oracle import regressor_oracle as R
-
-
-def _gen():
-    spec = importlib.util.spec_from_file_location(
-        "make_goldens_regressor", os.path.join(GOLDEN, "make_goldens_regressor.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def full_case(name):
-    """(args, latents, labels, fixture, meta) of a g5_full* fixture, inputs
-    regenerated from the recorded seed and checked by checksum."""
-    g = _gen()
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
-    with open(os.path.join(GOLDEN, name + ".json")) as f:
-        meta = json.load(f)
-    lat, lab = g.latents_and_labels(int(z["seed"]), noise=meta["noise"],
-                                    flip_valid=meta["flip_valid"])
-    assert np.allclose([g.checksum(l) for l in lat], z["lat_checksums"], rtol=0, atol=1e-9)
-    assert np.allclose([g.checksum(l) for l in lab], z["label_checksums"], rtol=0, atol=1e-9)
-    return dict(meta["args"]), lat, lab, z, meta
+from regressor_cases import full_case
 
 
 def _quiet(fn, *a):

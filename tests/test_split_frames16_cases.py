@@ -14,11 +14,11 @@ import itertools
 
 import pytest
 
+import abi_cases as ABI
 import frames16_cases as F
 import mmb_lib
 import split_frames16_cases as SF
-import test_frames16_cases as T16
-import test_lib_abi as ABI
+
 
 KINDS = list(SF.KINDS)
 NAME = "mmb_mm2_stream_split_ft"
@@ -37,7 +37,7 @@ def test_signature_mirrors_the_header():
     # ends mmb_mm2_stream
     ft, split = list(sig["mmb_mm2_stream_ft"][1]), list(sig["mmb_mm2_stream_split"][1])
     assert list(sig[NAME][1]) == ft[:-1] + split[-4:]
-    assert SF.ARGS[:-4] == T16.ARGS[:-1] and SF.ARGS[-4:] == ABI.ENTRY_ARGS["mmb_mm2_stream_split"][-4:]
+    assert SF.ARGS[:-4] == F.ARGS[:-1] and SF.ARGS[-4:] == ABI.ENTRY_ARGS["mmb_mm2_stream_split"][-4:]
     assert sig[NAME][0] is sig["mmb_mm2_stream_split"][0]
 
 
@@ -137,7 +137,7 @@ def test_keyword_on_the_split_is_the_f32_plan_s(kind):
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_keyword_on_at_pom_s_shape(kind):
-    shape = T16._shapes()["pom"]
+    shape = F._shapes()["pom"]
     assert (shape["n"], shape["t"]) == SF.POM_VALID[:2]
     import pipeline as PL
 
@@ -155,7 +155,7 @@ def test_keyword_on_at_pom_s_shape(kind):
 def test_keyword_changes_nothing_on_f32_frames(name):
     import pipeline as PL
 
-    shape = T16._shapes()[name]
+    shape = F._shapes()[name]
     plan = lambda **kw: PL.step_plan(d=300, npc=1, cus=CUS, n_total=shape["n"], **shape, **kw)  # noqa: E731
     for kw in ({}, dict(split_stream=True), dict(split_stream=False), dict(stream_project=False), dict(chunks=3),
                dict(narrow_fused=False), dict(fused_frames16=True, narrow_frames16=True)):
@@ -167,7 +167,7 @@ def test_keyword_changes_nothing_on_f32_frames(name):
 def test_the_three_keywords_together_give_the_f32_plan(name, kind):
     import pipeline as PL
 
-    shape = T16._shapes()[name]
+    shape = F._shapes()[name]
     plan = lambda **kw: PL.step_plan(d=300, npc=1, cus=CUS, n_total=shape["n"], **shape, **kw)  # noqa: E731
     all3 = dict(fused_frames16=True, narrow_frames16=True, split_frames16=True)
     for kw in ({}, dict(split_stream=True), dict(stream_project=True), dict(narrow_fused=False), dict(chunks=3)):

@@ -20,8 +20,8 @@ import frames16_cases as F
 import mmb2_cases as C
 import mmb_lib
 import table16_cases as T
-import test_frames16_cases as TF
 from frames16_cases import EINVAL, OK, P
+from table16_cases import OVERRIDES, _ids
 
 # ---------------------------------------------------------------- argument tables
 SIF_CASES = [("table_type -1", dict(table_type=-1), EINVAL),
@@ -59,10 +59,6 @@ STREAM_CASES += [(f"{tn} table, {what}", dict(table_type=tt, **change), want)
                      ("odd visual pointer, n 0", dict(visual=P + 3, n=0), EINVAL)])]
 
 
-def _ids(cases):
-    return [c[0].replace(" ", "_").replace(",", "") for c in cases]
-
-
 def test_signatures_mirror_the_header():
     assert len(mmb_lib.SIGNATURES["mmb_sif_wavg_tt"][1]) == len(T.SIF_ARGS)
     assert len(mmb_lib.SIGNATURES["mmb_mm2_stream_tt"][1]) == len(T.STREAM_ARGS)
@@ -91,16 +87,11 @@ def test_all_nine_pairs_are_in_the_table():
 
 
 # ---------------------------------------------------------------- the plan
-OVERRIDES = ({}, dict(stream_project=True, narrow_fused=True, split_stream=True),
-             dict(stream_project=True, narrow_fused=True, split_stream=True, fused_frames16=True,
-                  narrow_frames16=True, split_frames16=True))
-
-
 @pytest.mark.parametrize("name", ["c3", "mosi", "pom", "mid"])
 def test_step_plan_with_a_16_bit_table(name):
     import pipeline as PL
 
-    shape = TF._shapes()[name]
+    shape = F._shapes()[name]
     shape = {"n_total": shape["n"], **shape}
     plan = lambda **kw: PL.step_plan(d=300, npc=1, cus=256, **shape, **kw)  # noqa: E731
     # the f32 plan of the shape is not the two-kernel one (what the 16-bit table gives up) ...

@@ -33,9 +33,8 @@ import mmb_lib as L  # noqa: E402
 import models  # noqa: E402
 import pipeline as P  # noqa: E402
 import synth  # noqa: E402
+from mmb2_cases import TOL  # noqa: E402
 from oracle import mmb2_oracle as M  # noqa: E402
-
-TOL = 1e-5
 
 
 @contextlib.contextmanager

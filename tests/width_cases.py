@@ -1,6 +1,8 @@
 """Shared case tables and the input family of tests/test_gpu_widths.py (GPU)
 and tests/test_width_cases.py (CPU): the SIF / PC kernels at widths other
-than 300.  Plain helper module: no test is collected from it.
+than 300; and the bars of the SIF / PC path (EMB_TOL, F32_ROW, PC_BAR,
+SOLVE_BAR), which every GPU test of that path imports from here or through
+tests/common_gpu.py.  Plain helper module: no test is collected from it.
 
 Input family X(n, d): rows with two planted directions (so npc = 2 has a
 spectral gap) on 0.4 N(0, 1) noise, rounded to f32 and widened back, seeded
@@ -17,6 +19,12 @@ from oracle import sif_oracle as O
 
 N_OVERSAMPLES = 10
 NPCS = (1, 2, 6)
+
+# the bars the suite holds the SIF / PC path to, at 300 and at every other width
+EMB_TOL = 1e-5        # sentence embeddings, row-relative
+F32_ROW = 2.0 ** -23  # one f32 rounding (2^-24 of the element) with 2x margin, of the row's max
+PC_BAR = {1: 1e-10, 2: 1e-10, 6: 1e-8}  # per npc: the drop-ins' PCs against the oracle's
+SOLVE_BAR = {1: 1e-12, 2: 1e-10}        # per npc: the solvers against pc_from_gram of the same G, z0
 
 # (n, d): what each shape reaches in the dispatch of csrc/gram_kernels.hip,
 # csrc/pc_kernels.hip (X^T Omega, the solvers) and csrc/pc_remove_kernels.hip

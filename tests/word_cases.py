@@ -1,7 +1,8 @@
 """Shared case table, inputs and float64 reference of tests/test_gpu_word_widths.py
 (GPU) and tests/test_word_cases.py (CPU): the word log-likelihood kernels
-(csrc/latent_kernels.hip) at table widths other than 300.  Plain helper
-module: no test is collected from it.
+(csrc/latent_kernels.hip) at table widths other than 300; tests/test_gpu_scratch.py
+and tests/test_gpu_large.py hold their runs of these kernels to the same bars
+(lp_ratio, grad_ratio).  Plain helper module: no test is collected from it.
 
 word_zsum_kernel<NT> is instantiated per 16-column tile count NT = pad16(D) / 16
 = 1..20; the table below reaches NT 1, 2, 4, 7, 13, 19 and 20, a pad of 0, 1,
@@ -109,3 +110,18 @@ def reference(c, dense):
     for a in list(z.values()) + list(out[1:]):
         a.setflags(write=False)
     return out
+
+
+# ---------------------------------------------------------------- the bars, as fractions
+# (the ones tests/test_gpu_latent.py states: lp |y - y_ref| <= 2e-5 |y_ref| + 1e-4;
+#  the gradient, per row, max |g - g_ref| <= 2e-4 max |g_ref|)
+def lp_ratio(y, ref, rtol=2e-5, atol=1e-4):
+    y, ref = np.asarray(y, np.float64), np.asarray(ref, np.float64)
+    assert y.shape == ref.shape
+    return float((np.abs(y - ref) / (rtol * np.abs(ref) + atol)).max())
+
+
+def grad_ratio(g, ref, tol=2e-4):
+    g, ref = np.asarray(g, np.float64), np.asarray(ref, np.float64)
+    assert g.shape == ref.shape
+    return float((np.abs(g - ref).max(1) / (tol * np.abs(ref).max(1))).max())
