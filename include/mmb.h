@@ -14,6 +14,13 @@
  *     synchronises, so the calls can be captured into a hipGraph;
  *   - row-major, contiguous layouts; ids are int32 (the caller narrows the
  *     reference's int64 ids after a range check);
+ *   - a pointer carries no element type: the Python mirrors state each
+ *     operand's at the hand-over (mmb_lib.ptr(tensor, dtype): float -> float32,
+ *     double -> float64, int32_t / uint32_t -> int32, int64_t -> int64,
+ *     uint8_t -> uint8; a `void*` operand names the types it takes) and raise
+ *     before anything is launched on a tensor of another type, a host tensor
+ *     or a non-contiguous one (tests/test_presentation_cases.py reads the
+ *     types off this header);
  *   - return 0 on success, MMB_EINVAL (<0) on a bad argument or shape, or a
  *     positive hipError_t from the launch;
  *   - `flag` (nullable) is an int32 device word OR-ed with MMB_FLAG_* bits by

@@ -55,7 +55,7 @@ class WordTable:
         self.V, self.D = self.table.shape
         self.Dp = L.query("mmb_word_pad", self.D)
         self.wn = torch.empty((self.V, self.Dp), dtype=torch.float32, device=dev)
-        L.call("mmb_word_normalize", L.ptr(self.table), self.V, self.D, L.ptr(self.wn),
+        L.call("mmb_word_normalize", L.ptr(self.table, L.F32), self.V, self.D, L.ptr(self.wn, L.F32),
                L.stream_ptr())
 
 
@@ -63,15 +63,24 @@ _table_cache: dict = {}
 
 
 def word_table(word_embeddings: torch.Tensor) -> WordTable:
-    """Cached WordTable for a (device) table tensor — keyed by storage and version,
-    so an in-place edit of the table is noticed."""
+    """WordTable of a table tensor, cached for a float32 contiguous device
+    tensor — keyed by storage and version, so an in-place edit of the table is
+    noticed.  Any other input (a host tensor, float64, a strided view) is
+    normalised from its current values on every call: WordTable then holds a
+    copy, nothing keeps the input's storage alive or tells an edit of it (the
+    memory under a torch.from_numpy tensor, a write through `.data`) from the
+    values the copy was made of, and another table or view at the same
+    address would hit the same entry."""
+    if not (word_embeddings.is_cuda and word_embeddings.dtype == torch.float32
+            and word_embeddings.is_contiguous()):
+        return WordTable(word_embeddings)
     key = (word_embeddings.data_ptr(), tuple(word_embeddings.shape), word_embeddings._version,
-           str(word_embeddings.device), word_embeddings.dtype)
+           str(word_embeddings.device))
     wt = _table_cache.get(key)
     if wt is None:
         if len(_table_cache) > 8:
             _table_cache.clear()
-        wt = WordTable(word_embeddings)
+        wt = WordTable(word_embeddings)  # (wt.table shares the input's storage and keeps it alive)
         _table_cache[key] = wt
     return wt
 
@@ -93,10 +102,11 @@ class _WordLogProb(torch.autograd.Function):
         state = torch.empty((B, 4), dtype=torch.float32, device=dev) if want else None
         gsum = torch.empty((B, table.Dp), dtype=torch.float32, device=dev) if want else None
         cosv = torch.empty((B, Lt), dtype=torch.float32, device=dev) if want else None
-        L.call("mmb_word_logprob_forward", L.ptr(lat), B, D, L.ptr(table.wn), table.V, L.ptr(ids),
-               L.ptr(table.table) if ids is not None else None, L.ptr(sent_dense), Lt, L.ptr(w),
-               L.ptr(mask), float(a), int(want), L.ptr(ws), L.ptr(lp), L.ptr(state), L.ptr(gsum),
-               L.ptr(cosv), L.stream_ptr())
+        L.call("mmb_word_logprob_forward", L.ptr(lat, L.F32), B, D, L.ptr(table.wn, L.F32), table.V,
+               L.ptr(ids, L.I32), L.ptr(table.table, L.F32) if ids is not None else None,
+               L.ptr(sent_dense, L.F32), Lt, L.ptr(w, L.F32), L.ptr(mask, L.F32), float(a), int(want),
+               L.ptr(ws, L.BYTES), L.ptr(lp, L.F32), L.ptr(state, L.F32), L.ptr(gsum, L.F32),
+               L.ptr(cosv, L.F32), L.stream_ptr())
         if want:
             ctx.save_for_backward(lat, ids, sent_dense, w, mask, state, gsum, cosv)
             ctx.table, ctx.a = table, a
@@ -108,10 +118,11 @@ class _WordLogProb(torch.autograd.Function):
         table = ctx.table
         B, D = lat.shape
         dlat = torch.empty_like(lat)
-        L.call("mmb_word_logprob_backward", L.ptr(lat), B, D, table.V, L.ptr(ids),
-               L.ptr(table.table) if ids is not None else None, L.ptr(sent_dense), w.shape[1],
-               L.ptr(w), L.ptr(mask), float(ctx.a), L.ptr(state), L.ptr(gsum), L.ptr(cosv),
-               L.ptr(dlp.float().contiguous()), L.ptr(dlat), L.stream_ptr())
+        L.call("mmb_word_logprob_backward", L.ptr(lat, L.F32), B, D, table.V, L.ptr(ids, L.I32),
+               L.ptr(table.table, L.F32) if ids is not None else None, L.ptr(sent_dense, L.F32),
+               w.shape[1], L.ptr(w, L.F32), L.ptr(mask, L.F32), float(ctx.a), L.ptr(state, L.F32),
+               L.ptr(gsum, L.F32), L.ptr(cosv, L.F32), L.ptr(dlp.float().contiguous(), L.F32),
+               L.ptr(dlat, L.F32), L.stream_ptr())
         return dlat, None, None, None, None, None, None
 
 
@@ -137,12 +148,39 @@ def gauss_stats(x: torch.Tensor, mask: torch.Tensor | None = None) -> torch.Tens
     m = None
     if mask is not None:
         m = mask.detach().to(device=x.device, dtype=torch.float32).expand(N, T, F).contiguous()
-    L.call("mmb_gauss_stats", L.ptr(x), L.ptr(m), N, T, F, L.ptr(st), L.stream_ptr())
+    L.call("mmb_gauss_stats", L.ptr(x, L.F32), L.ptr(m, L.F32), N, T, F, L.ptr(st, L.F64), L.stream_ptr())
     return st
 
 
-def _ptr_array(ts, ctype=ctypes.c_void_p):
-    return (ctype * len(ts))(*[0 if t is None else t.data_ptr() for t in ts])
+def _ptr_array(ts, dtype):
+    """void*[len(ts)] of contiguous device tensors of `dtype` (None: a null
+    entry), every address through L.ptr's checks."""
+    return (ctypes.c_void_p * len(ts))(*[L.ptr(t, dtype) or 0 for t in ts])
+
+
+def _rows_array(ts, dtype, widths, lds=None):
+    """(void*[K], int64[K]) of the strided entry points' row blocks: [B, F_k]
+    views of `dtype` with unit column stride (None: a null entry with the
+    stride of `lds`), every address and row stride through L.rows_ptr's
+    checks.  With `lds` each block must have that row stride (a key's gradient
+    shares its input's: the kernel walks both with one)."""
+    K = len(ts)
+    ptrs, strides = [], []
+    for k, (t, f) in enumerate(zip(ts, widths)):
+        want = None if lds is None else lds[k]
+        if t is None:
+            if want is None:
+                raise L.MMBError("a null row block needs the row stride of its input")
+            a, ld = 0, want
+        else:
+            a, ld = L.rows_ptr(t, dtype, f)
+            if want is not None and t.shape[0] <= 1:
+                ld = want  # (one row has no row stride of its own)
+            if want is not None and ld != want:
+                raise L.MMBError(f"key {k}: row stride {ld} differs from its input's {want}")
+        ptrs.append(a)
+        strides.append(ld)
+    return (ctypes.c_void_p * K)(*ptrs), (ctypes.c_int64 * K)(*strides)
 
 
 class GaussStats:
@@ -153,32 +191,43 @@ class GaussStats:
         self.fm = [0 if s is None else s.shape[2] for s in self.stats]
 
 
+def _key_widths(gs: GaussStats, mods) -> list[int]:
+    """F_k of every key: the widths of its modalities' frame sums."""
+    return [sum(f for bit, f in zip((1, 2, 4), gs.fm) if m & bit) for m in mods]
+
+
 def _rows(t: torch.Tensor):
-    """(tensor, row stride) for the strided Gaussian entry points: a [B, F]
-    view with unit column stride passes as is (e.g. a key's column block of
-    the generator's fused output), anything else as a contiguous copy."""
+    """A mu / sigma as the strided Gaussian entry points take it: a [B, F]
+    view with unit column stride and rows at least its width apart passes as
+    is (e.g. a key's column block of the generator's fused output), anything
+    else as a contiguous copy -- a broadcast mu / sigma (row stride 0, the
+    reference's [1, 1, F] expanded over the batch) among them; autograd sums
+    its gradient back over the batch."""
     t = t.detach()
-    if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+    if (t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1
+            or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
         t = t.float().contiguous()
-    return t, t.stride(0)
+    return t  # (a host tensor is refused at the hand-over: L.rows_ptr)
 
 
 class _GaussLogProb(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gs: GaussStats, idx, mods, *musig):
         K = len(mods)
-        mus, ldm = zip(*[_rows(m) for m in musig[:K]])
-        sigs, lds = zip(*[_rows(s) for s in musig[K:]])
+        mus = [_rows(m) for m in musig[:K]]
+        sigs = [_rows(s) for s in musig[K:]]
         B = mus[0].shape[0]
         L.check_grid("gauss_log_prob", B)
         lp = torch.empty((K, B), dtype=torch.float32, device=mus[0].device)
-        st = _ptr_array(gs.stats)
+        widths = _key_widths(gs, mods)
+        st = _ptr_array(gs.stats, L.F64)
         fm = (ctypes.c_int * 3)(*gs.fm)
         md = (ctypes.c_int * K)(*mods)
-        L.call("mmb_gauss_loglik_strided", st, fm, L.ptr(idx), B, K, md, _ptr_array(mus),
-               (ctypes.c_int64 * K)(*ldm), _ptr_array(sigs), (ctypes.c_int64 * K)(*lds), L.ptr(lp),
-               L.stream_ptr())
-        ctx.gs, ctx.mods, ctx.ldm, ctx.lds = gs, mods, ldm, lds
+        pmu, ldm = _rows_array(mus, L.F32, widths)
+        psg, lds = _rows_array(sigs, L.F32, widths)
+        L.call("mmb_gauss_loglik_strided", st, fm, L.ptr(idx, L.I64), B, K, md, pmu, ldm, psg, lds,
+               L.ptr(lp, L.F32), L.stream_ptr())
+        ctx.gs, ctx.mods, ctx.ldm, ctx.lds = gs, mods, tuple(ldm), tuple(lds)
         ctx.save_for_backward(idx, *mus, *sigs)
         return lp
 
@@ -198,6 +247,12 @@ class _GaussLogProb(torch.autograd.Function):
             # the gradients reach the split / linear backward without copies
             if not any(need):
                 return [None] * K
+
+            def own(t, ld):
+                # a buffer of the key's own, rows `ld` apart like its input's (a
+                # strided view's empty_like would come back dense)
+                return torch.empty((B, ld), dtype=torch.float32, device=t.device)[:, :t.shape[1]]
+
             base = ts[0]
             same = all(t.stride(0) == lds[0] and t.untyped_storage().data_ptr() ==
                        base.untyped_storage().data_ptr() for t in ts)
@@ -209,25 +264,26 @@ class _GaussLogProb(torch.autograd.Function):
                 blocks = sorted((t.storage_offset(), t.shape[1]) for t, n in zip(ts, need) if n)
                 same = all(o0 + w0 <= o1 for (o0, w0), (o1, _) in zip(blocks, blocks[1:]))
             if not same:
-                return [torch.empty_like(t) if n else None for t, n in zip(ts, need)]
+                return [own(t, ld) if n else None for t, ld, n in zip(ts, lds, need)]
             lo = min(t.storage_offset() for t in ts)
             width = max(t.storage_offset() - lo + t.shape[1] for t in ts)
             buf = torch.empty((B, lds[0]), dtype=torch.float32, device=base.device)
             return [buf[:, t.storage_offset() - lo:t.storage_offset() - lo + t.shape[1]] if n
                     else None for t, n in zip(ts, need)] if width <= lds[0] else \
-                [torch.empty_like(t) if n else None for t, n in zip(ts, need)]
+                [own(t, ld) if n else None for t, ld, n in zip(ts, lds, need)]
 
         dmu = grads(mus, ctx.ldm, need_mu)
         dsg = grads(sigs, ctx.lds, need_s)
-        ldm = [d.stride(0) if d is not None else l for d, l in zip(dmu, ctx.ldm)]
-        lds = [d.stride(0) if d is not None else l for d, l in zip(dsg, ctx.lds)]
-        # (a key's gradient must share its input's row stride: the kernel walks both with one)
-        assert all(a == b for a, b in zip(ldm, ctx.ldm)) and all(a == b for a, b in zip(lds, ctx.lds))
         gs = ctx.gs
-        L.call("mmb_gauss_backward_strided", _ptr_array(gs.stats), (ctypes.c_int * 3)(*gs.fm),
-               L.ptr(idx), B, K, (ctypes.c_int * K)(*ctx.mods), _ptr_array(mus),
-               (ctypes.c_int64 * K)(*ctx.ldm), _ptr_array(sigs), (ctypes.c_int64 * K)(*ctx.lds),
-               L.ptr(dlp.float().contiguous()), _ptr_array(dmu), _ptr_array(dsg), L.stream_ptr())
+        widths = _key_widths(gs, ctx.mods)
+        pmu, ldm = _rows_array(mus, L.F32, widths, ctx.ldm)
+        psg, lds = _rows_array(sigs, L.F32, widths, ctx.lds)
+        # (a key's gradient shares its input's row stride: the kernel walks both with one)
+        pdmu, _ = _rows_array(dmu, L.F32, widths, ctx.ldm)
+        pdsg, _ = _rows_array(dsg, L.F32, widths, ctx.lds)
+        L.call("mmb_gauss_backward_strided", _ptr_array(gs.stats, L.F64), (ctypes.c_int * 3)(*gs.fm),
+               L.ptr(idx, L.I64), B, K, (ctypes.c_int * K)(*ctx.mods), pmu, ldm, psg, lds,
+               L.ptr(dlp.float().contiguous(), L.F32), pdmu, pdsg, L.stream_ptr())
         return (None, None, None, *dmu, *dsg)
 
 
@@ -263,8 +319,9 @@ class _LayerNorm(torch.autograd.Function):
         dx = torch.empty_like(x2)
         dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         db = torch.empty_like(w) if ctx.needs_input_grad[2] else None
-        L.call("mmb_layer_norm_backward", L.ptr(dy2), L.ptr(x2), L.ptr(mean), L.ptr(rstd),
-               L.ptr(w), N, D, L.ptr(dx), L.ptr(dw), L.ptr(db), L.stream_ptr())
+        L.call("mmb_layer_norm_backward", L.ptr(dy2, L.F32), L.ptr(x2, L.F32), L.ptr(mean, L.F32),
+               L.ptr(rstd, L.F32), L.ptr(w, L.F32), N, D, L.ptr(dx, L.F32), L.ptr(dw, L.F32),
+               L.ptr(db, L.F32), L.stream_ptr())
         return dx.view(ctx.shape), dw, db, None
 
 

@@ -205,14 +205,54 @@ def require_gpu() -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def ptr(t) -> int | None:
+# The element types of the C ABI's pointer parameters (include/mmb.h): what a
+# mirror states at every hand-over.  `uint32_t*` words are int32 tensors.
+F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
+# the `void*` operands: a word table or a frame tensor of any kind the kernels
+# read, the s buffer (fp16 hi | lo planes or fp32), a byte workspace or image
+TABLE = FRAMES = (torch.float32, torch.float16, torch.bfloat16)
+S_BUF = (torch.float16, torch.float32)
+BYTES = (torch.uint8,)
+WORDS = (torch.uint8, torch.float32)  # a workspace the caller may hold as bytes or as f32 words
+
+
+def ptr(t, dtype=None) -> int | None:
+    """The device address of `t` for a parameter of element type `dtype` (a
+    torch dtype, or a tuple of them for a `void*` operand that takes several);
+    None passes as a null pointer.  MMBError, before anything is launched, for
+    a host tensor, a non-contiguous one, or another element type: the C ABI
+    takes a bare pointer and would read the bytes as its own type."""
     if t is None:
         return None
-    if not t.is_cuda:
-        raise MMBError("libmmb entry points take device tensors")
+    # (one test on the step's eager path; the checks below name what failed)
+    if (dtype is None or t.dtype is dtype) and t.is_cuda and t.is_contiguous():
+        return t.data_ptr()
+    _check_operand(t, dtype)
     if not t.is_contiguous():
         raise MMBError("libmmb entry points take contiguous tensors")
     return t.data_ptr()
+
+
+def _check_operand(t, dtype) -> None:
+    """The element type (None: not stated) and the device of an operand."""
+    if dtype is not None and t.dtype is not dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):
+        want = " or ".join(map(str, dtype)) if isinstance(dtype, tuple) else str(dtype)
+        raise MMBError(f"libmmb entry point takes {want} here, not a {t.dtype} tensor")
+    if not t.is_cuda:
+        raise MMBError("libmmb entry points take device tensors")
+
+
+def rows_ptr(t, dtype, width: int):
+    """(address, row stride) of a [B, width] operand of the strided entry
+    points: rows of `dtype` with unit column stride, `ld >= width` elements
+    apart (a column block of a wider tensor).  The checks of ptr(), with the
+    rows' layout in place of contiguity."""
+    _check_operand(t, dtype)
+    if (t.dim() != 2 or t.shape[1] != width or (width > 1 and t.stride(1) != 1)
+            or (t.shape[0] > 1 and t.stride(0) < width)):
+        raise MMBError(f"libmmb strided entry points take [B, {width}] rows with unit column stride "
+                       f"and a row stride >= {width}, not shape {tuple(t.shape)} strides {t.stride()}")
+    return t.data_ptr(), max(t.stride(0), width)
 
 
 def stream_ptr(stream=None) -> int:

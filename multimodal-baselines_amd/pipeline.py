@@ -94,8 +94,8 @@ def seq2weight(seq32: torch.Tensor, sel: torch.Tensor | None, wtab64: torch.Tens
                flag: torch.Tensor | None = None) -> torch.Tensor:
     n, l = seq32.shape
     w = torch.empty((n, l), dtype=torch.float32, device=seq32.device)
-    L.call("mmb_seq2weight", L.ptr(seq32), L.ptr(sel), n, l, L.ptr(wtab64), wtab64.numel(),
-           L.ptr(w), L.ptr(flag), L.stream_ptr())
+    L.call("mmb_seq2weight", L.ptr(seq32, L.I32), L.ptr(sel, L.U8), n, l, L.ptr(wtab64, L.F64),
+           wtab64.numel(), L.ptr(w, L.F32), L.ptr(flag, L.I32), L.stream_ptr())
     return w
 
 
@@ -139,17 +139,17 @@ def weighted_sum(table: torch.Tensor, ids32: torch.Tensor, w: torch.Tensor | Non
     dev = table.device
     kind = table_kind(table, "weighted_sum")
     # the entry point and its table arguments: a 16-bit table carries its type
-    entry, tab = (("mmb_sif_wavg", (L.ptr(table),)) if kind == "f32" else
-                  ("mmb_sif_wavg_tt", (L.ptr(table), TABLE_KINDS[kind][1])))
+    entry, tab = (("mmb_sif_wavg", (L.ptr(table, L.F32),)) if kind == "f32" else
+                  ("mmb_sif_wavg_tt", (L.ptr(table, L.TABLE), TABLE_KINDS[kind][1])))
     if x_out:
         x = torch.empty((n, D), dtype=torch.float32, device=dev)
-        L.call(entry, *tab, V, D, L.ptr(ids32), n, l, L.ptr(w), L.ptr(wtab32),
-               L.ptr(x), None, None, L.ptr(flag), L.stream_ptr())
+        L.call(entry, *tab, V, D, L.ptr(ids32, L.I32), n, l, L.ptr(w, L.F32), L.ptr(wtab32, L.F32),
+               L.ptr(x, L.F32), None, None, L.ptr(flag, L.I32), L.stream_ptr())
         return x
     num = torch.empty((n, D), dtype=torch.float32, device=dev)
     cnt = torch.empty((n,), dtype=torch.float32, device=dev)
-    L.call(entry, *tab, V, D, L.ptr(ids32), n, l, L.ptr(w), L.ptr(wtab32),
-           None, L.ptr(num), L.ptr(cnt), L.ptr(flag), L.stream_ptr())
+    L.call(entry, *tab, V, D, L.ptr(ids32, L.I32), n, l, L.ptr(w, L.F32), L.ptr(wtab32, L.F32),
+           None, L.ptr(num, L.F32), L.ptr(cnt, L.F32), L.ptr(flag, L.I32), L.stream_ptr())
     return num, cnt
 
 
@@ -173,8 +173,8 @@ def gram(num: torch.Tensor, cnt: torch.Tensor | None, G: torch.Tensor | None = N
         G = torch.empty((d, d), dtype=torch.float64, device=num.device)
     if ws is None or not ws.fits(n, d):
         ws = GramWorkspace(n, d, num.device)
-    L.call("mmb_gram", L.ptr(num), L.ptr(cnt), n, d, L.ptr(G), int(accumulate), L.ptr(ws.buf),
-           L.stream_ptr())
+    L.call("mmb_gram", L.ptr(num, L.F32), L.ptr(cnt, L.F32), n, d, L.ptr(G, L.F64), int(accumulate),
+           L.ptr(ws.buf, L.BYTES), L.stream_ptr())
     return G
 
 
@@ -185,7 +185,7 @@ def colmax(x: torch.Tensor, out: torch.Tensor | None = None, accumulate: bool = 
     L.check_grid("colmax", n, 256)
     if out is None:
         out = torch.empty((d,), dtype=torch.int32, device=x.device)
-    L.call("mmb_colmax", L.ptr(x), n, d, L.ptr(out), int(accumulate), L.stream_ptr())
+    L.call("mmb_colmax", L.ptr(x, L.F32), n, d, L.ptr(out, L.I32), int(accumulate), L.stream_ptr())
     return out
 
 
@@ -198,8 +198,8 @@ def gram_i8(x: torch.Tensor, cmax: torch.Tensor, G: torch.Tensor | None = None,
         G = torch.empty((d, d), dtype=torch.float64, device=x.device)
     if ws is None or not ws.fits(n, d):
         ws = GramWorkspace(n, d, x.device)
-    L.call("mmb_gram_i8", L.ptr(x), L.ptr(cmax), n, d, L.ptr(G), int(accumulate), L.ptr(ws.buf),
-           L.stream_ptr())
+    L.call("mmb_gram_i8", L.ptr(x, L.F32), L.ptr(cmax, L.I32), n, d, L.ptr(G, L.F64), int(accumulate),
+           L.ptr(ws.buf, L.BYTES), L.stream_ptr())
     return G
 
 
@@ -207,8 +207,8 @@ def xt_omega(num, cnt, omega_rows: torch.Tensor) -> torch.Tensor:
     n, d = num.shape
     k = omega_rows.shape[1]
     z0 = torch.empty((d, k), dtype=torch.float64, device=num.device)
-    L.call("mmb_xt_omega", L.ptr(num), L.ptr(cnt), n, d, L.ptr(omega_rows), k, L.ptr(z0),
-           L.stream_ptr())
+    L.call("mmb_xt_omega", L.ptr(num, L.F32), L.ptr(cnt, L.F32), n, d, L.ptr(omega_rows, L.F64), k,
+           L.ptr(z0, L.F64), L.stream_ptr())
     return z0
 
 
@@ -254,15 +254,15 @@ def pc_solve(G: torch.Tensor, z0: torch.Tensor, npc: int, transposed: bool,
         own = flag is None
         if own:
             flag = torch.zeros(1, dtype=torch.int32, device=G.device)
-        L.call("mmb_pc_solve_mc", L.ptr(G), d, L.ptr(z0), k, npc, n_iter, int(transposed),
-               L.ptr(pc), L.ptr(ws), L.ptr(flag), L.stream_ptr())
+        L.call("mmb_pc_solve_mc", L.ptr(G, L.F64), d, L.ptr(z0, L.F64), k, npc, n_iter, int(transposed),
+               L.ptr(pc, L.F64), L.ptr(ws, L.BYTES), L.ptr(flag, L.I32), L.stream_ptr())
         if own and int(flag.item()) & L.MMB_FLAG_SYNC_TIMEOUT:
             ws[:16].zero_()  # an aborted solve leaves its control words set
             raise RuntimeError("mmb_pc_solve_mc: a bounded hand-over between the solver's "
                                "workgroups timed out; the PC is invalid (NaN)")
     else:
-        L.call("mmb_pc_solve", L.ptr(G), d, L.ptr(z0), k, npc, n_iter, int(transposed), L.ptr(pc),
-               L.stream_ptr())
+        L.call("mmb_pc_solve", L.ptr(G, L.F64), d, L.ptr(z0, L.F64), k, npc, n_iter, int(transposed),
+               L.ptr(pc, L.F64), L.stream_ptr())
     return pc
 
 
@@ -271,10 +271,11 @@ def remove_pc(num, cnt, pc: torch.Tensor, out_dtype=torch.float32, out=None) -> 
     n, d = num.shape
     if out is None:
         out = torch.empty((n, d), dtype=out_dtype, device=num.device)
-    o32 = L.ptr(out) if out.dtype == torch.float32 else None
-    o64 = L.ptr(out) if out.dtype == torch.float64 else None
-    L.call("mmb_pc_remove", L.ptr(num), L.ptr(cnt), n, d, L.ptr(pc), pc.shape[0], o32, o64,
-           L.stream_ptr())
+    if out.dtype not in (torch.float32, torch.float64):
+        raise L.MMBError(f"remove_pc writes float32 or float64 rows, not {out.dtype}")
+    L.call("mmb_pc_remove", L.ptr(num, L.F32), L.ptr(cnt, L.F32), n, d, L.ptr(pc, L.F64), pc.shape[0],
+           L.ptr(out, L.F32) if out.dtype == torch.float32 else None,
+           L.ptr(out, L.F64) if out.dtype == torch.float64 else None, L.stream_ptr())
     return out
 
 
@@ -286,7 +287,7 @@ def pc_f64(x64: torch.Tensor, npc: int) -> torch.Tensor:
     n, d = x64.shape
     G = torch.empty((d, d), dtype=torch.float64, device=x64.device)
     ws = GramWorkspace(n, d, x64.device)
-    L.call("mmb_gram_f64", L.ptr(x64), n, d, L.ptr(G), 0, L.ptr(ws.buf), L.stream_ptr())
+    L.call("mmb_gram_f64", L.ptr(x64, L.F64), n, d, L.ptr(G, L.F64), 0, L.ptr(ws.buf, L.BYTES), L.stream_ptr())
     z0, transposed = pc_start_block(x64, None, npc, n, ops=F64Ops)
     return pc_solve(G, z0, npc, transposed)
 
@@ -295,14 +296,15 @@ def xt_omega_f64(x64, cnt, omega_rows: torch.Tensor) -> torch.Tensor:
     n, d = x64.shape
     k = omega_rows.shape[1]
     z0 = torch.empty((d, k), dtype=torch.float64, device=x64.device)
-    L.call("mmb_xt_omega_f64", L.ptr(x64), n, d, L.ptr(omega_rows), k, L.ptr(z0), L.stream_ptr())
+    L.call("mmb_xt_omega_f64", L.ptr(x64, L.F64), n, d, L.ptr(omega_rows, L.F64), k, L.ptr(z0, L.F64),
+           L.stream_ptr())
     return z0
 
 
 def remove_pc_f64(x64: torch.Tensor, pc: torch.Tensor) -> torch.Tensor:
     n, d = x64.shape
     out = torch.empty((n, d), dtype=torch.float64, device=x64.device)
-    L.call("mmb_pc_remove_f64", L.ptr(x64), n, d, L.ptr(pc), pc.shape[0], L.ptr(out),
+    L.call("mmb_pc_remove_f64", L.ptr(x64, L.F64), n, d, L.ptr(pc, L.F64), pc.shape[0], L.ptr(out, L.F64),
            L.stream_ptr())
     return out
 
@@ -391,8 +393,8 @@ def calc_weights(x: torch.Tensor, b_mean: torch.Tensor, b_log_sigma: torch.Tenso
     f = x.shape[-1]
     qm = torch.empty_like(x)
     qs = torch.empty_like(x)
-    L.call("mmb_calc_weights", L.ptr(x), x.numel() // f, f, L.ptr(b_mean.contiguous()),
-           L.ptr(b_log_sigma.contiguous()), L.ptr(qm), L.ptr(qs), L.stream_ptr())
+    L.call("mmb_calc_weights", L.ptr(x, L.F32), x.numel() // f, f, L.ptr(b_mean.contiguous(), L.F32),
+           L.ptr(b_log_sigma.contiguous(), L.F32), L.ptr(qm, L.F32), L.ptr(qs, L.F32), L.stream_ptr())
     return qm, qs
 
 
@@ -445,12 +447,12 @@ class MMB2Projection:
     def refresh(self):
         self.params = [tuple(p.detach().to(device=self.device, dtype=torch.float32).contiguous()
                              for p in ps) for ps in self._live()]
-        arr = lambda i: (ctypes_ptr_array([p[i].data_ptr() for p in self.params]))
+        arr = lambda i: (ctypes_ptr_array([L.ptr(p[i], L.F32) for p in self.params]))
         L.call("mmb_mm2_prepare", arr(0), arr(1), arr(2), arr(3), self.d, self.a, self.vd, self.t,
-               L.ptr(self.wm), self.ldw, L.ptr(self.c0), L.ptr(self.wsplit), L.stream_ptr())
+               L.ptr(self.wm, L.F32), self.ldw, L.ptr(self.c0, L.F32), L.ptr(self.wsplit, L.BYTES), L.stream_ptr())
         if getattr(self, "wpieces", None) is not None:
-            L.call("mmb_mm2_split_pieces", L.ptr(self.wm), self.d, self.a, self.vd, self.ldw,
-                   L.ptr(self.wpieces), L.stream_ptr())
+            L.call("mmb_mm2_split_pieces", L.ptr(self.wm, L.F32), self.d, self.a, self.vd, self.ldw,
+                   L.ptr(self.wpieces, L.BYTES), L.stream_ptr())
         if getattr(self, "text_cache", None) is not None:
             self._build_text_cache()
         self._seen = self._versions()
@@ -481,8 +483,8 @@ class MMB2Projection:
 
     def _build_text_cache(self):
         table, wtab32 = self.text_src
-        L.call("mmb_mm2_text_cache", L.ptr(table), table.shape[0], self.d, L.ptr(wtab32),
-               L.ptr(self.wm), self.ldw, L.ptr(self.text_cache), L.stream_ptr())
+        L.call("mmb_mm2_text_cache", L.ptr(table, L.F32), table.shape[0], self.d, L.ptr(wtab32, L.F32),
+               L.ptr(self.wm, L.F32), self.ldw, L.ptr(self.text_cache, L.BYTES), L.stream_ptr())
 
     def enable_pieces(self):
         """Also keep the piece-ordered split of wm (mmb_mm2_split_pieces), the
@@ -491,8 +493,8 @@ class MMB2Projection:
             nbytes = L.query("mmb_mm2_split_pieces_bytes", self.d, self.a, self.vd)
             self.wpieces = torch.empty((nbytes + 15) // 16 * 16, dtype=torch.uint8,
                                        device=self.wm.device)
-            L.call("mmb_mm2_split_pieces", L.ptr(self.wm), self.d, self.a, self.vd, self.ldw,
-                   L.ptr(self.wpieces), L.stream_ptr())
+            L.call("mmb_mm2_split_pieces", L.ptr(self.wm, L.F32), self.d, self.a, self.vd, self.ldw,
+                   L.ptr(self.wpieces, L.BYTES), L.stream_ptr())
 
     def refresh_if_changed(self) -> bool:
         """Re-merge only when a generator parameter changed since the last
@@ -620,19 +622,22 @@ def mm2_stream(n, t, d, a, vd, audio, visual, ids32=None, table=None, wtab32=Non
     V = table.shape[0] if table is not None else 0
     # the arguments the three entry points share: the gathered text's, the
     # frames', and everything from the shapes on
-    gathered = (L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32))
-    frames = (L.ptr(audio), L.ptr(visual))
-    tail = (n, t, d, a, vd, L.ptr(num), L.ptr(s), int(s_half), L.ptr(aux), L.ptr(flag),
-            L.ptr(colmax), L.ptr(colmax_ws))
-    text = (*gathered, L.ptr(text_dense), L.ptr(emb_dense), L.ptr(w_dense))
+    # (a 16-bit table or frame type reaches only the entry points that take its `void*`)
+    table_t = L.F32 if tkind == "f32" else L.TABLE
+    frame_t = L.F32 if kind == "f32" else L.FRAMES
+    gathered = (L.ptr(ids32, L.I32), L.ptr(table, table_t), V, L.ptr(wtab32, L.F32))
+    frames = (L.ptr(audio, frame_t), L.ptr(visual, frame_t))
+    tail = (n, t, d, a, vd, L.ptr(num, L.F32), L.ptr(s, L.S_BUF), int(s_half), L.ptr(aux, L.F32),
+            L.ptr(flag, L.I32), L.ptr(colmax, L.I32), L.ptr(colmax_ws, L.BYTES))
+    text = (*gathered, L.ptr(text_dense, L.F32), L.ptr(emb_dense, L.F32), L.ptr(w_dense, L.F32))
     if split is not None:
-        L.call("mmb_mm2_stream_split", *text, *frames, *tail, int(parts), L.ptr(split),
+        L.call("mmb_mm2_stream_split", *text, *frames, *tail, int(parts), L.ptr(split, L.BYTES),
                split.numel() * split.element_size(), L.stream_ptr())
     elif tkind != "f32":
-        L.call("mmb_mm2_stream_tt", L.ptr(ids32), L.ptr(table), TABLE_KINDS[tkind][1], V, L.ptr(wtab32),
-               L.ptr(w_dense), *frames, FRAME_KINDS[kind][1], *tail, L.stream_ptr())
+        L.call("mmb_mm2_stream_tt", gathered[0], gathered[1], TABLE_KINDS[tkind][1], V, gathered[3],
+               L.ptr(w_dense, L.F32), *frames, FRAME_KINDS[kind][1], *tail, L.stream_ptr())
     elif kind != "f32":
-        L.call("mmb_mm2_stream_ft", *gathered, L.ptr(w_dense), *frames, FRAME_KINDS[kind][1], *tail,
+        L.call("mmb_mm2_stream_ft", *gathered, L.ptr(w_dense, L.F32), *frames, FRAME_KINDS[kind][1], *tail,
                L.stream_ptr())
     else:
         L.call("mmb_mm2_stream", *text, *frames, *tail, L.stream_ptr())
@@ -659,10 +664,11 @@ def mm2_stream_split_ft(n, t, d, a, vd, audio, visual, ids32, table, wtab32=None
     if split is None:
         split = split_ws(n, t, d, a, vd, audio.device, parts)
     V = table.shape[0] if table is not None else 0
-    L.call("mmb_mm2_stream_split_ft", L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32), L.ptr(w_dense),
-           L.ptr(audio), L.ptr(visual), FRAME_KINDS[kind][1], n, t, d, a, vd, L.ptr(num), L.ptr(s),
-           int(s_half), L.ptr(aux), L.ptr(flag), L.ptr(colmax), L.ptr(colmax_ws), int(parts), L.ptr(split),
-           split.numel() * split.element_size(), L.stream_ptr())
+    L.call("mmb_mm2_stream_split_ft", L.ptr(ids32, L.I32), L.ptr(table, L.F32), V, L.ptr(wtab32, L.F32),
+           L.ptr(w_dense, L.F32), L.ptr(audio, L.FRAMES), L.ptr(visual, L.FRAMES), FRAME_KINDS[kind][1],
+           n, t, d, a, vd, L.ptr(num, L.F32), L.ptr(s, L.S_BUF), int(s_half), L.ptr(aux, L.F32),
+           L.ptr(flag, L.I32), L.ptr(colmax, L.I32), L.ptr(colmax_ws, L.BYTES), int(parts),
+           L.ptr(split, L.BYTES), split.numel() * split.element_size(), L.stream_ptr())
     return num, s, aux
 
 
@@ -715,10 +721,13 @@ def _stream_project(entry: str, ft: bool, cache: bool, text: tuple, n, t, d, a, 
         proj.enable_pieces()
     num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
     V = table.shape[0] if table is not None else 0
-    L.call("mmb_" + entry, L.ptr(ids32), L.ptr(table), V, L.ptr(wtab32),
-           *([L.ptr(proj.text_cache)] if cache else []), *map(L.ptr, text), L.ptr(audio), L.ptr(visual),
-           *([FRAME_KINDS[kind][1]] if ft else []), n, t, d, a, vd, L.ptr(proj.wpieces), L.ptr(proj.c0),
-           L.ptr(num), L.ptr(aux), L.ptr(mmb2), L.ptr(flag), L.ptr(colmax), L.ptr(colmax_ws), L.stream_ptr())
+    frame_t = L.FRAMES if ft else L.F32  # (`const void*` with a frame_type, else `const float*`)
+    L.call("mmb_" + entry, L.ptr(ids32, L.I32), L.ptr(table, L.F32), V, L.ptr(wtab32, L.F32),
+           *([L.ptr(proj.text_cache, L.BYTES)] if cache else []), *[L.ptr(x, L.F32) for x in text],
+           L.ptr(audio, frame_t), L.ptr(visual, frame_t), *([FRAME_KINDS[kind][1]] if ft else []),
+           n, t, d, a, vd, L.ptr(proj.wpieces, L.BYTES), L.ptr(proj.c0, L.F32), L.ptr(num, L.F32),
+           L.ptr(aux, L.F32), L.ptr(mmb2, L.F32), L.ptr(flag, L.I32), L.ptr(colmax, L.I32),
+           L.ptr(colmax_ws, L.BYTES), L.stream_ptr())
     return num, aux, mmb2
 
 
@@ -775,10 +784,11 @@ def mm2_stream_project_tt(n, t, d, a, vd, audio, visual, proj: "MMB2Projection",
     tkind = table_kind(table, who)
     proj.enable_pieces()
     num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
-    L.call("mmb_" + who, L.ptr(ids32), L.ptr(table), TABLE_KINDS[tkind][1], table.shape[0], L.ptr(wtab32),
-           L.ptr(w_dense), L.ptr(audio), L.ptr(visual), FRAME_KINDS[kind][1], n, t, d, a, vd,
-           L.ptr(proj.wpieces), L.ptr(proj.c0), L.ptr(num), L.ptr(aux), L.ptr(mmb2), L.ptr(flag),
-           L.ptr(colmax), L.ptr(colmax_ws), L.stream_ptr())
+    L.call("mmb_mm2_stream_project_tt", L.ptr(ids32, L.I32), L.ptr(table, L.TABLE), TABLE_KINDS[tkind][1],
+           table.shape[0], L.ptr(wtab32, L.F32), L.ptr(w_dense, L.F32), L.ptr(audio, L.FRAMES),
+           L.ptr(visual, L.FRAMES), FRAME_KINDS[kind][1], n, t, d, a, vd, L.ptr(proj.wpieces, L.BYTES),
+           L.ptr(proj.c0, L.F32), L.ptr(num, L.F32), L.ptr(aux, L.F32), L.ptr(mmb2, L.F32),
+           L.ptr(flag, L.I32), L.ptr(colmax, L.I32), L.ptr(colmax_ws, L.BYTES), L.stream_ptr())
     return num, aux, mmb2
 
 
@@ -839,21 +849,23 @@ def mm2_project(s, num, aux, proj: MMB2Projection, out=None, pc=None, sif_out=No
     if pc is not None and (s.dtype != torch.float16 or pc.shape[0] != 1 or sif_out is None):
         raise L.MMBError("fused PC removal needs fp16 s, npc = 1 and sif_out")
     if split is not None and s.dtype == torch.float16:
-        L.call("mmb_mm2_project_x3_split", L.ptr(s), L.ptr(num), L.ptr(aux), L.ptr(proj.wsplit),
-               proj.ldw, L.ptr(proj.c0), n, proj.kp, proj.d, L.ptr(out), L.ptr(pc),
-               L.ptr(sif_out), int(slices), L.ptr(split), split.numel(), L.stream_ptr())
+        L.call("mmb_mm2_project_x3_split", L.ptr(s, L.S_BUF), L.ptr(num, L.F32), L.ptr(aux, L.F32),
+               L.ptr(proj.wsplit, L.BYTES), proj.ldw, L.ptr(proj.c0, L.F32), n, proj.kp, proj.d,
+               L.ptr(out, L.F32), L.ptr(pc, L.F64), L.ptr(sif_out, L.F32), int(slices),
+               L.ptr(split, L.BYTES), split.numel(), L.stream_ptr())
         return out
     if pc is not None:
-        L.call("mmb_mm2_project_x3_rmpc", L.ptr(s), L.ptr(num), L.ptr(aux), L.ptr(proj.wsplit),
-               proj.ldw, L.ptr(proj.c0), n, proj.kp, proj.d, L.ptr(out), L.ptr(pc),
-               L.ptr(sif_out), L.stream_ptr())
+        L.call("mmb_mm2_project_x3_rmpc", L.ptr(s, L.S_BUF), L.ptr(num, L.F32), L.ptr(aux, L.F32),
+               L.ptr(proj.wsplit, L.BYTES), proj.ldw, L.ptr(proj.c0, L.F32), n, proj.kp, proj.d,
+               L.ptr(out, L.F32), L.ptr(pc, L.F64), L.ptr(sif_out, L.F32), L.stream_ptr())
         return out
     if s.dtype == torch.float32:
-        L.call("mmb_mm2_project", L.ptr(s), L.ptr(num), L.ptr(aux), L.ptr(proj.wm), proj.ldw,
-               L.ptr(proj.c0), n, proj.kp, proj.d, L.ptr(out), L.stream_ptr())
+        L.call("mmb_mm2_project", L.ptr(s, L.F32), L.ptr(num, L.F32), L.ptr(aux, L.F32), L.ptr(proj.wm, L.F32),
+               proj.ldw, L.ptr(proj.c0, L.F32), n, proj.kp, proj.d, L.ptr(out, L.F32), L.stream_ptr())
     elif s.dtype == torch.float16:
-        L.call("mmb_mm2_project_x3", L.ptr(s), L.ptr(num), L.ptr(aux), L.ptr(proj.wsplit),
-               proj.ldw, L.ptr(proj.c0), n, proj.kp, proj.d, L.ptr(out), L.stream_ptr())
+        L.call("mmb_mm2_project_x3", L.ptr(s, L.S_BUF), L.ptr(num, L.F32), L.ptr(aux, L.F32),
+               L.ptr(proj.wsplit, L.BYTES), proj.ldw, L.ptr(proj.c0, L.F32), n, proj.kp, proj.d,
+               L.ptr(out, L.F32), L.stream_ptr())
     else:
         raise L.MMBError(f"unsupported s dtype {s.dtype}")
     return out
@@ -1150,6 +1162,11 @@ class FusedStep:
         # the word table's, likewise: a 16-bit table takes the two-kernel step
         # (or, with fused_table16, the fused front's mm2_stream_project_tt)
         self.table_kind = table_kind(self.table, "FusedStep")
+        # and the ids' and the weight table's: int64 ids would be read as
+        # pairs of int32, float64 weights as pairs of float32
+        for what, t, dtype in (("ids", self.ids, torch.int32), ("wtab", inputs["wtab"], torch.float32)):
+            if t is not None and t.dtype != dtype:
+                raise L.MMBError(f"FusedStep: inputs[{what!r}] must be {dtype}, not {t.dtype}")
         self.plan = p = step_plan(self.n, self.n_total, self.t, self.d, self.a, self.vd, self.V, npc,
                                   L.cu_count(dev), chunks=chunks, fuse_remove=fuse_remove,
                                   gram_kind=gram_kind, stream_project=stream_project,
@@ -1242,8 +1259,8 @@ class FusedStep:
             out = torch.empty(1, dtype=torch.int32, device=flag.device)
         # one launch (mmb_step_status): eight elementwise torch kernels here
         # were ~40 us of every dataset split's graph (r06 kernel trace)
-        L.call("mmb_step_status", L.ptr(flag), L.ptr(pc), pc.numel(), PC_NONFINITE, L.ptr(out),
-               L.stream_ptr())
+        L.call("mmb_step_status", L.ptr(flag, L.I32), L.ptr(pc, L.F64), pc.numel(), PC_NONFINITE,
+               L.ptr(out, L.I32), L.stream_ptr())
         return out
 
     def raise_status(self, v: int):
@@ -1294,8 +1311,8 @@ class FusedStep:
         """Chunk c's rows into G (or into the partials of mmb_gram_finish)."""
         r0, r1 = self.bounds[c]
         if self.gram_parts:
-            L.call("mmb_gram_part", L.ptr(self.x[r0:r1]), None, r1 - r0,
-                   self.step_rows, self.d, int(c > 0), L.ptr(self.gws.buf), L.stream_ptr())
+            L.call("mmb_gram_part", L.ptr(self.x[r0:r1], L.F32), None, r1 - r0,
+                   self.step_rows, self.d, int(c > 0), L.ptr(self.gws.buf, L.BYTES), L.stream_ptr())
         elif self.gram_i8:  # one chunk
             gram_i8(self.x, self.colmax, self.G, ws=self.gws)
         else:
@@ -1339,9 +1356,9 @@ class FusedStep:
             # solve (mmb_pc_solve_mc_xt)
             om = omega(self.n_total, k, self.table.device)
             with mark("pc_solve"):
-                L.call("mmb_pc_solve_mc_xt", L.ptr(self.G), d, L.ptr(self.x), self.n, L.ptr(om), k,
-                       self.npc, N_ITER, L.ptr(self.pc_buf), L.ptr(self.solve_ws), L.ptr(self.flag),
-                       L.stream_ptr())
+                L.call("mmb_pc_solve_mc_xt", L.ptr(self.G, L.F64), d, L.ptr(self.x, L.F32), self.n,
+                       L.ptr(om, L.F64), k, self.npc, N_ITER, L.ptr(self.pc_buf, L.F64),
+                       L.ptr(self.solve_ws, L.BYTES), L.ptr(self.flag, L.I32), L.stream_ptr())
             return self.pc_buf
         with mark("pc_start"):
             z0, transposed = pc_start_block(self.x, None, self.npc, self.n_total, self.row0)
@@ -1411,8 +1428,8 @@ class FusedStep:
             self._gram(last)
         if p.gram == "parts":
             with mark("gram_finish"):
-                L.call("mmb_gram_finish", p.step_rows, self.d, L.ptr(self.G), 0,
-                       L.ptr(self.gws.buf), L.stream_ptr())
+                L.call("mmb_gram_finish", p.step_rows, self.d, L.ptr(self.G, L.F64), 0,
+                       L.ptr(self.gws.buf, L.BYTES), L.stream_ptr())
         pc = self._solve(mark)
         if p.remove_launch:
             with mark("pc_remove"):

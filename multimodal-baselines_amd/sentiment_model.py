@@ -79,9 +79,9 @@ class _Regressor(torch.autograd.Function):
         L.check_grid("SentimentModel", b, 2)  # (the backward's rows per workgroup; the forward takes 8)
         y = torch.empty((b, o), dtype=torch.float32, device=x.device)
         hid = torch.empty((b, h), dtype=torch.float32, device=x.device)
-        L.call("mmb_mlp_forward_train", L.ptr(x), b, d, h, o, L.ptr(w1.detach()),
-               L.ptr(b1.detach()), L.ptr(w2.detach()), L.ptr(b2.detach()), L.ptr(y), L.ptr(hid),
-               L.stream_ptr())
+        L.call("mmb_mlp_forward_train", L.ptr(x, L.F32), b, d, h, o, L.ptr(w1.detach(), L.F32),
+               L.ptr(b1.detach(), L.F32), L.ptr(w2.detach(), L.F32), L.ptr(b2.detach(), L.F32),
+               L.ptr(y, L.F32), L.ptr(hid, L.F32), L.stream_ptr())
         ctx.save_for_backward(x, hid, w1, w2)
         return y
 
@@ -96,9 +96,10 @@ class _Regressor(torch.autograd.Function):
         dw1, db1 = (e(h, d) if need[1] else None), (e(h) if need[2] else None)
         dw2, db2 = (e(o, h) if need[3] else None), (e(o) if need[4] else None)
         dh = e(b, h)
-        L.call("mmb_mlp_backward", L.ptr(x), L.ptr(hid), b, d, h, o, L.ptr(w1.detach()),
-               L.ptr(w2.detach()), L.ptr(dy.float().contiguous()), L.ptr(dh), L.ptr(dx),
-               L.ptr(dw1), L.ptr(db1), L.ptr(dw2), L.ptr(db2), L.stream_ptr())
+        L.call("mmb_mlp_backward", L.ptr(x, L.F32), L.ptr(hid, L.F32), b, d, h, o, L.ptr(w1.detach(), L.F32),
+               L.ptr(w2.detach(), L.F32), L.ptr(dy.float().contiguous(), L.F32), L.ptr(dh, L.F32),
+               L.ptr(dx, L.F32), L.ptr(dw1, L.F32), L.ptr(db1, L.F32), L.ptr(dw2, L.F32),
+               L.ptr(db2, L.F32), L.stream_ptr())
         return dx, dw1, db1, dw2, db2
 
 
@@ -131,8 +132,8 @@ class SentimentModel(nn.Module):
         L.check_grid("SentimentModel", x.shape[0], 32)
         y = torch.empty((x.shape[0], o), dtype=torch.float32, device=dev)
         with torch.no_grad():
-            L.call("mmb_mlp_forward", L.ptr(x), None, x.shape[0], d, h, o, L.ptr(w1), L.ptr(b1),
-                   L.ptr(w2), L.ptr(b2), L.ptr(y), L.stream_ptr())
+            L.call("mmb_mlp_forward", L.ptr(x, L.F32), None, x.shape[0], d, h, o, L.ptr(w1, L.F32),
+                   L.ptr(b1, L.F32), L.ptr(w2, L.F32), L.ptr(b2, L.F32), L.ptr(y, L.F32), L.stream_ptr())
         return y.reshape(*lead, o).squeeze().to(home)
 
 
@@ -207,8 +208,9 @@ def _evaluate(loader, model, latents, dev):
     L.check_grid("evaluate", n, loader.batch_size)
     bl = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
     pred = torch.empty((max(n, 1), o), dtype=torch.float32, device=dev)
-    L.call("mmb_mlp_eval", L.ptr(lat), L.ptr(lab), L.ptr(perm), n, loader.batch_size, d, h, o,
-           L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), L.ptr(bl), L.ptr(pred), L.stream_ptr())
+    L.call("mmb_mlp_eval", L.ptr(lat, L.F32), L.ptr(lab, L.F32), L.ptr(perm, L.I64), n, loader.batch_size,
+           d, h, o, L.ptr(w1, L.F32), L.ptr(b1, L.F32), L.ptr(w2, L.F32), L.ptr(b2, L.F32),
+           L.ptr(bl, L.F32), L.ptr(pred, L.F32), L.stream_ptr())
     return bl[:nb], pred[:n], perm, lab
 
 
@@ -281,14 +283,15 @@ def train_sentiment(args, model, train_data, train_latents, valid_data, valid_la
         if in_kernel and vperms:
             vperm = torch.cat(vperms).to(dev)
             vloss = torch.empty(len(vperms) * nbv, dtype=torch.float32, device=dev)
-            vargs = (L.ptr(vlat), L.ptr(vlab), L.ptr(vperm), n_valid, valid_niter, i, L.ptr(vloss))
+            vargs = (L.ptr(vlat, L.F32), L.ptr(vlab, L.F32), L.ptr(vperm, L.I64), n_valid, valid_niter, i,
+                     L.ptr(vloss, L.F32))
         else:
             vloss = None
             vargs = (None, None, None, 0, 1, i, None)
         w1r = w1 if dp == d else torch.nn.functional.pad(w1.detach(), (0, dp - d)).contiguous()
-        L.call("mmb_mlp_train", L.ptr(lat), L.ptr(lab), L.ptr(perm), n_samples, block, B, dp, h, o,
-               float(lr), L.ptr(w1r), L.ptr(b1), L.ptr(w2), L.ptr(b2), L.ptr(step_loss), *vargs,
-               L.ptr(ws), L.ptr(flag), L.stream_ptr())
+        L.call("mmb_mlp_train", L.ptr(lat, L.F32), L.ptr(lab, L.F32), L.ptr(perm, L.I64), n_samples, block, B,
+               dp, h, o, float(lr), L.ptr(w1r, L.F32), L.ptr(b1, L.F32), L.ptr(w2, L.F32), L.ptr(b2, L.F32),
+               L.ptr(step_loss, L.F32), *vargs, L.ptr(ws, L.WORDS), L.ptr(flag, L.I32), L.stream_ptr())
         if dp != d:
             with torch.no_grad():
                 w1.copy_(w1r[:, :d])

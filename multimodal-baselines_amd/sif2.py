@@ -117,8 +117,8 @@ def estimate_embedding_overall_gpu2(data, masks, networks, sentence_weights, emb
             raise ValueError("N * L must be < 2^31")
         rows = torch.arange(n * l, device=dev, dtype=torch.int32).view(n, l)
         # x -> num (the a2 row), count_nonzero(w) -> aux[0], in one a2 pass
-        L.call("mmb_sif_wavg", L.ptr(emb), n * l, d, L.ptr(rows), n, l, L.ptr(sw), None,
-               L.ptr(num), None, L.ptr(aux[0]), None, L.stream_ptr())
+        L.call("mmb_sif_wavg", L.ptr(emb, L.F32), n * l, d, L.ptr(rows, L.I32), n, l, L.ptr(sw, L.F32), None,
+               L.ptr(num, L.F32), None, L.ptr(aux[0], L.F32), None, L.stream_ptr())
         aux[1].copy_(sw.sum(-1))  # sentence_weights.sum(-1), sif2.py:186
     if n == 1:
         # the reference squeezes the batch dim away (sif2.py:200-201) and then

@@ -17,6 +17,26 @@ def declared_functions():
     return sorted(set(re.findall(r"\b(mmb_[a-z0-9_]+)\s*\(", src)))
 
 
+def prototypes():
+    """name -> [(C type, parameter name), ...] of every entry point the header
+    declares, the type with `const` dropped and its `*`s kept ("float*",
+    "void* const*", "int64_t")."""
+    src = open(HEADER).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    out = {}
+    for name, body in re.findall(r"\b(mmb_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
+        params = []
+        for p in (q.strip() for q in body.split(",")):
+            if p == "void" or not p:
+                continue
+            m = re.fullmatch(r"(.*?)(\w+)", p, flags=re.S)
+            ctype = " ".join(m.group(1).split())
+            ctype = re.sub(r"\s*\*\s*", "*", re.sub(r"^const ", "", ctype)).replace("*const*", "* const*")
+            params.append((ctype, m.group(2)))
+        out[name] = params
+    return out
+
+
 STREAM = ("ids table v wtab32 text_dense emb_dense w_dense audio visual n t d a vd num_out s_out "
           "s_half aux_out flag colmax colmax_ws").split()
 ENTRY_ARGS = {
