@@ -425,6 +425,46 @@ int mmb_mm2_stream_split_ft(const int32_t* ids, const float* table, int64_t v, c
                             int s_half, float* aux_out, int32_t* flag, uint32_t* colmax,
                             void* colmax_ws, int parts, void* ws, size_t ws_bytes, hipStream_t stream);
 
+/* mmb_mm2_stream_split_ft on a word table kept in 16-bit storage as well: table
+ * [v,d] contiguous holds elements of table_type (MMB_TABLE_*, as
+ * mmb_sif_wavg_tt), the frames elements of frame_type; all nine pairs are
+ * taken.  Text is gathered (ids + table, weights from wtab32 or per token from
+ * w_dense).  Only the text workgroups and the second kernel read the table: a
+ * table value is widened to f32 in registers right after its (plain, cached)
+ * load -- exact for both 16-bit types, fp16 subnormals included -- and enters
+ * the weighted sum, the text sums Sx_e / Sxx_e and the row-0 shortcut (row 0
+ * once, as w0 E0, c0 E0, c0 E0^2) by the statements of the f32 kernels in
+ * their order; the partial sums in ws are f32 and the frame workgroups do not
+ * know the table's type.  Every output -- x, s (both s_half formats), the
+ * three aux planes, the column bounds and the flag word -- is bit for bit what
+ * mmb_mm2_stream_split_ft writes, with the same parts, for the same table
+ * upcast to f32 by the caller (and, with one range, what mmb_mm2_stream_tt's
+ * workgroup kernel writes for the 16-bit table).  The library rounds nothing.
+ * parts, ws (mmb_mm2_stream_split_ws_bytes: the same bytes for every table and
+ * frame type), the plan (mmb_mm2_stream_split_parts), outputs, layouts, the
+ * empty call (n == 0, before the workspace is looked at) and the flag bits are
+ * mmb_mm2_stream_split's; like it the call never synchronises, never allocates
+ * and can be captured into a graph.
+ * MMB_TABLE_F32 is mmb_mm2_stream_split_ft itself for the same arguments.
+ * 16-bit table: the text in 4-value units (one 8-byte load) when d % 4 == 0
+ * and the table is 8-byte aligned (d up to 1280), in scalar 2-byte loads if
+ * not (d up to 320); row offsets are 64-bit (id * d); the frames follow
+ * mmb_mm2_stream_split_ft's rules for their type; 3 d + 2 a + 2 vd <= 2240 as
+ * for f32.
+ * MMB_EINVAL before any launch: a table_type outside 0..2 (also with n == 0),
+ * a 16-bit table that is not 2-byte aligned, null ids, anything
+ * mmb_mm2_stream_split_ft rejects.
+ * replaces: the frame loops of sif2.estimate_embedding_overall_gpu2
+ *   sif2.py:181-205 and the gathers at simplesif.py:862-871 (which read an f32
+ *   table only) at the per-split call sites simplesif.py:308-311 (POM's long
+ *   transcripts)                                                             */
+int mmb_mm2_stream_split_tt(const int32_t* ids, const void* table, int table_type, int64_t v,
+                            const float* wtab32, const float* w_dense, const void* audio,
+                            const void* visual, int frame_type, int64_t n, int t, int d, int a, int vd,
+                            float* num_out, void* s_out, int s_half, float* aux_out, int32_t* flag,
+                            uint32_t* colmax, void* colmax_ws, int parts, void* ws, size_t ws_bytes,
+                            hipStream_t stream);
+
 /* mmb_mm2_stream and mmb_mm2_project_x3 in ONE kernel (the bench step's
  * MMB2 path): the same num (x), aux[0..1] and colmax outputs as mmb_mm2_stream
  * (aux[2] is the text piece's scale) and the MMB2 rows of mmb_mm2_project_x3
@@ -656,6 +696,60 @@ int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* table, int64_
  * replaces: sif2.calc_weights + estimate_embedding_overall_gpu2
  *   /root/reference/sif2.py:103-114,164-208 (which reads f32 frames only)    */
 int mmb_mm2_stream_project_narrow_ft(const int32_t* ids, const float* table, int64_t v,
+                                     const float* wtab32, const void* text_cache, const void* audio,
+                                     const void* visual, int frame_type, int64_t n, int t, int d,
+                                     int a, int vd, const void* wpieces, const float* c0,
+                                     float* num_out, float* aux_out, float* mmb2_out, int32_t* flag,
+                                     uint32_t* colmax, void* colmax_ws, hipStream_t stream);
+
+/* mmb_mm2_text_cache from a word table kept in 16-bit storage: table [v,d]
+ * contiguous holds elements of table_type (MMB_TABLE_*, as mmb_sif_wavg_tt).
+ * A table value is widened to f32 right after its (scalar 2-byte) load --
+ * exact for both 16-bit types, fp16 subnormals included: the E half of a cache
+ * row is the widened value, the P half the same f64 fma chain over it, rounded
+ * once.  The cache has mmb_mm2_text_cache's layout and
+ * mmb_mm2_text_cache_bytes(v, d) bytes and is byte for byte the cache
+ * mmb_mm2_text_cache builds from the same table upcast to f32 by the caller
+ * -- the hot-word id slots v .. 31 of a table of v < 32 words stay unwritten,
+ * as there.  The library rounds nothing.  Rebuild rules, v <= 16384 and the
+ * 16-byte aligned cache are mmb_mm2_text_cache's; like it the call never
+ * synchronises, never allocates and can be captured into a graph.  There is
+ * no empty call (v > 0).
+ * MMB_TABLE_F32 is mmb_mm2_text_cache itself for the same arguments.
+ * MMB_EINVAL before any launch: a table_type outside 0..2, a 16-bit table that
+ * is not 2-byte aligned, anything mmb_mm2_text_cache rejects.
+ * replaces: the text rows of sif2.estimate_embedding_overall_gpu2
+ *   /root/reference/sif2.py:186-205 over the gathers at simplesif.py:862-871
+ *   (which read an f32 table only)                                           */
+int mmb_mm2_text_cache_tt(const void* table, int table_type, int64_t v, int d, const float* wtab32,
+                          const float* wm, int ldw, void* cache, hipStream_t stream);
+
+/* mmb_mm2_stream_project_narrow_ft for a word table kept in 16-bit storage:
+ * table [v,d] contiguous holds elements of table_type (MMB_TABLE_*), the
+ * frames elements of frame_type; all nine pairs are taken.  The kernel takes
+ * its text -- table rows and their projections -- from the text cache (f32
+ * E | P rows, here built by mmb_mm2_text_cache_tt from the same table) and
+ * the token weights from the cache's copy of wtab32: `table` is NOT read by
+ * the launch, so the table's type selects no other kernel and only sets what
+ * the pointer is held to.  Every output -- x, the three aux planes, the MMB2
+ * rows, the column bounds and the flag word -- is bit for bit what
+ * mmb_mm2_stream_project_narrow_ft writes for the same table upcast to f32 by
+ * the caller with a cache built from it.  The library rounds nothing.  Shapes
+ * (mmb_mm2_stream_project_narrow_supported, unchanged), outputs, layouts, the
+ * empty call (n == 0) and the flag bits are mmb_mm2_stream_project_narrow's;
+ * like it the call never synchronises, never allocates and can be captured
+ * into a graph.
+ * MMB_TABLE_F32 is mmb_mm2_stream_project_narrow_ft itself for the same
+ * arguments (a 16-byte aligned table).
+ * MMB_EINVAL before any launch, every output untouched: a table_type outside
+ * 0..2 (also with n == 0), a 16-bit table that is not 2-byte aligned (its
+ * element; text cache, num_out, mmb2_out and wpieces stay 16-byte aligned,
+ * the frames aligned to a unit of their type), anything
+ * mmb_mm2_stream_project_narrow_ft rejects.
+ * replaces: sif2.calc_weights + estimate_embedding_overall_gpu2
+ *   /root/reference/sif2.py:103-114,164-208 with the text gather of
+ *   /root/reference/simplesif.py:862-871 (which reads an f32 table only)     */
+int mmb_mm2_stream_project_narrow_tt(const int32_t* ids, const void* table, int table_type, int64_t v,
                                      const float* wtab32, const void* text_cache, const void* audio,
                                      const void* visual, int frame_type, int64_t n, int t, int d,
                                      int a, int vd, const void* wpieces, const float* c0,

@@ -13,6 +13,7 @@
 // division by the total weight and the row L2 normalisation (:207) fused into
 // its epilogue.
 #include "mmb_common.h"
+#include "mmb_text_cache.h"
 
 namespace mmb {
 
@@ -1293,30 +1294,8 @@ namespace mmb {
 // (kTextLdp, kTextLdq, kTextHot: mmb_common.h, shared with that kernel)
 constexpr int64_t kTextMaxV = 16384;
 
-__global__ __launch_bounds__(320) void mm2_text_table_kernel(const float* __restrict__ E, int D,
-                                                             const float* __restrict__ wm, int ldw,
-                                                             float* __restrict__ rows) {
-  __shared__ double se[kTextLdp], se2[kTextLdp];
-  const int64_t v = blockIdx.x;
-  for (int f = threadIdx.x; f < D; f += blockDim.x) {
-    const double e = E[v * D + f];
-    se[f] = e;
-    se2[f] = e * e;
-  }
-  __syncthreads();
-  float* row = rows + v * kTextLdq;
-  for (int f = threadIdx.x; f < D; f += blockDim.x) row[f] = E[v * D + f];
-  for (int j = threadIdx.x; j + D < kTextLdq; j += blockDim.x) {
-    double acc = 0.0;
-    if (j <= D) {
-      for (int f = 0; f < D; ++f) {
-        acc = fma(se[f], static_cast<double>(wm[static_cast<int64_t>(f) * ldw + j]), acc);
-        acc = fma(se2[f], static_cast<double>(wm[static_cast<int64_t>(D + f) * ldw + j]), acc);
-      }
-    }
-    row[D + j] = static_cast<float>(acc);
-  }
-}
+// (the row kernel, mm2_text_table_kernel<TE>: mmb_text_cache.h -- this source
+// instantiates it for an f32 table)
 
 // rank of each word among the weights (ascending; ties: lower id first):
 // hot_slot1[v] = rank + 1 for the k smallest, else 0; hot_ids[rank] = v
@@ -1352,21 +1331,39 @@ extern "C" size_t mmb_mm2_text_cache_bytes(int64_t v, int d) {
   return sizeof(float) * static_cast<size_t>(v) * (kTextLdq + 1) + sizeof(int32_t) * (v + kTextHot);
 }
 
-extern "C" int mmb_mm2_text_cache(const float* table, int64_t v, int d, const float* wtab32,
-                                  const float* wm, int ldw, void* cache, hipStream_t stream) {
+// mmb_mm2_text_cache and mmb_mm2_text_cache_tt on a table of storage type
+// table_type (validated by the caller): the checks, the rows from the kernel
+// instantiated for the table type, the hot words.
+static int text_cache(int table_type, const void* table, int64_t v, int d, const float* wtab32, const float* wm,
+                      int ldw, void* cache, hipStream_t stream) {
   MMB_REQUIRE(table && wtab32 && wm && cache && v > 0 && v <= kTextMaxV);
   MMB_REQUIRE(d > 0 && d % 4 == 0 && d + 1 <= kTextLdp && ldw > d && aligned16(cache));
+  // a 16-bit value is never read from an odd address
+  MMB_REQUIRE(table_type == MMB_TABLE_F32 || (reinterpret_cast<uintptr_t>(table) & 1) == 0);
   float* ptab = static_cast<float*>(cache);
   int32_t* hot_slot1 = reinterpret_cast<int32_t*>(ptab + static_cast<size_t>(v) * kTextLdq);
   int32_t* hot_ids = hot_slot1 + v;
   float* wcopy = reinterpret_cast<float*>(hot_ids + kTextHot);
-  mm2_text_table_kernel<<<static_cast<unsigned>(v), 320, 0, stream>>>(table, d, wm, ldw, ptab);
-  MMB_LAUNCH_CHECK();
+  const int rc = table_type == MMB_TABLE_F32   ? text_table_rows<float>(table, v, d, wm, ldw, ptab, stream)
+                 : table_type == MMB_TABLE_F16 ? text_table_rows_f16(table, v, d, wm, ldw, ptab, stream)
+                                               : text_table_rows_bf16(table, v, d, wm, ldw, ptab, stream);
+  if (rc != MMB_OK) return rc;
   text_hot_kernel<<<static_cast<unsigned>(ceil_div(v, 1024)), 1024, 0, stream>>>(
       wtab32, static_cast<int>(v), static_cast<int>(std::min<int64_t>(v, kTextHot)), hot_slot1, hot_ids,
       wcopy);
   MMB_LAUNCH_CHECK();
   return MMB_OK;
+}
+
+extern "C" int mmb_mm2_text_cache(const float* table, int64_t v, int d, const float* wtab32,
+                                  const float* wm, int ldw, void* cache, hipStream_t stream) {
+  return text_cache(MMB_TABLE_F32, table, v, d, wtab32, wm, ldw, cache, stream);
+}
+
+extern "C" int mmb_mm2_text_cache_tt(const void* table, int table_type, int64_t v, int d, const float* wtab32,
+                                     const float* wm, int ldw, void* cache, hipStream_t stream) {
+  MMB_REQUIRE(table_bytes(table_type) != 0);
+  return text_cache(table_type, table, v, d, wtab32, wm, ldw, cache, stream);
 }
 
 // the tools build's projection variants, launches and knobs (tools/diag/);

@@ -1,6 +1,8 @@
 // What the stream sources share (narrow_fused_kernels.hip, through
-// mmb_stream_kernels.h the three SIF sources and, through mmb_fused.h, the
-// three fused sources; included by them only): the
+// mmb_stream_kernels.h the three SIF sources, through mmb_fused.h the fused
+// sources, through mmb_split_kernels.h and mmb_text_cache.h the two split_tab
+// sources and, for the element types, mm2_kernels.hip; included by them
+// only): the
 // kernels' argument block and limits, the frame and table element types, the device
 // helpers more than one kernel family uses, and the declarations of the entry
 // points' host-side front end (defined once, in sif_kernels.hip).  No

@@ -1,6 +1,7 @@
 // The MMB2 stream and its projection in one kernel at narrow frame widths:
-// utt_narrow_fused_kernel (f32, fp16 and bf16 frames), mmb_mm2_stream_project_narrow
-// and mmb_mm2_stream_project_narrow_ft.
+// utt_narrow_fused_kernel (f32, fp16 and bf16 frames), mmb_mm2_stream_project_narrow,
+// mmb_mm2_stream_project_narrow_ft and mmb_mm2_stream_project_narrow_tt (a
+// 16-bit word table: the same kernels, whose text comes from the cache).
 #include "mmb_stream.h"
 
 namespace mmb {
@@ -585,15 +586,20 @@ extern "C" int mmb_mm2_stream_project_narrow_supported(int t, int d, int a_, int
          v * (kNFLdq + 2) * 4 + 4 * kNFHot < (int64_t{1} << 31) && static_cast<int64_t>(t) * (a_ > vd ? a_ : vd) * 4 < (int64_t{1} << 31);
 }
 
-// mmb_mm2_stream_project_narrow for frames of storage type frame_type
-// (MMB_FRAMES_*, validated by the caller): the checks, the text cache, the
-// rows per wave, the grid and the column bounds are the same for the three.
-static int narrow_project(int frame_type, const int32_t* ids, const float* table, int64_t v,
+// mmb_mm2_stream_project_narrow for a word table of storage type table_type
+// and frames of storage type frame_type (MMB_TABLE_* / MMB_FRAMES_*, validated
+// by the caller): the checks, the text cache, the rows per wave, the grid and
+// the column bounds are the same for all.  The kernel takes its text from the
+// cache (ptab: the E | P rows, f32 whatever the table's type) and never reads
+// `table`, so the table's type picks no instantiation: it only sets what the
+// pointer is held to.
+static int narrow_project(int table_type, int frame_type, const int32_t* ids, const void* table_, int64_t v,
                           const float* wtab32, const void* text_cache, const void* audio,
                           const void* visual, int64_t n, int t, int d, int a_, int vd, const void* wpieces,
                           const float* c0, float* num_out, float* aux_out, float* mmb2_out, int32_t* flag,
                           uint32_t* colmax, void* colmax_ws, hipStream_t stream) {
   NarrowFusedArgs f{};
+  const float* table = static_cast<const float*>(table_);
   // gathered text with the weight table only; the sums stay on chip
   MMB_REQUIRE(ids && wtab32);
   if (const int rc = stream_args(&f.s, ids, table, v, wtab32, nullptr, nullptr, nullptr, audio, visual, n, t, d,
@@ -602,7 +608,9 @@ static int narrow_project(int frame_type, const int32_t* ids, const float* table
   MMB_REQUIRE(n < (int64_t{1} << 31) - kNFRows && mmb_mm2_stream_project_narrow_supported(t, d, a_, vd, v));
   MMB_REQUIRE(text_cache && mmb2_out && wpieces && c0);
   // (stream_vec's width % 4 asks nothing new: the predicate above has it)
-  const StreamVec vec = stream_vec(f.s, frame_bytes(frame_type));
+  StreamVec vec = stream_vec(f.s, frame_bytes(frame_type));
+  // a 16-bit table (not read by the launch) is held to its element's alignment
+  if (table_type != MMB_TABLE_F32) vec.t = (reinterpret_cast<uintptr_t>(table) & 1) == 0;
   MMB_REQUIRE(vec.t && vec.a && vec.v && aligned16(text_cache) && aligned16(num_out) && aligned16(mmb2_out) &&
               aligned16(wpieces));
   if (n == 0) return empty_call(colmax, d, stream);
@@ -662,8 +670,8 @@ extern "C" int mmb_mm2_stream_project_narrow(const int32_t* ids, const float* ta
                                              const float* c0, float* num_out, float* aux_out,
                                              float* mmb2_out, int32_t* flag, uint32_t* colmax,
                                              void* colmax_ws, hipStream_t stream) {
-  return narrow_project(MMB_FRAMES_F32, ids, table, v, wtab32, text_cache, audio, visual, n, t, d, a_, vd, wpieces,
-                        c0, num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
+  return narrow_project(MMB_TABLE_F32, MMB_FRAMES_F32, ids, table, v, wtab32, text_cache, audio, visual, n, t, d, a_,
+                        vd, wpieces, c0, num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
 }
 
 extern "C" int mmb_mm2_stream_project_narrow_ft(const int32_t* ids, const float* table, int64_t v,
@@ -674,8 +682,20 @@ extern "C" int mmb_mm2_stream_project_narrow_ft(const int32_t* ids, const float*
                                                 float* mmb2_out, int32_t* flag, uint32_t* colmax,
                                                 void* colmax_ws, hipStream_t stream) {
   MMB_REQUIRE(frame_bytes(frame_type) != 0);
-  return narrow_project(frame_type, ids, table, v, wtab32, text_cache, audio, visual, n, t, d, a_, vd, wpieces, c0,
-                        num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
+  return narrow_project(MMB_TABLE_F32, frame_type, ids, table, v, wtab32, text_cache, audio, visual, n, t, d, a_, vd,
+                        wpieces, c0, num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
+}
+
+extern "C" int mmb_mm2_stream_project_narrow_tt(const int32_t* ids, const void* table, int table_type, int64_t v,
+                                                const float* wtab32, const void* text_cache,
+                                                const void* audio, const void* visual, int frame_type,
+                                                int64_t n, int t, int d, int a_, int vd, const void* wpieces,
+                                                const float* c0, float* num_out, float* aux_out,
+                                                float* mmb2_out, int32_t* flag, uint32_t* colmax,
+                                                void* colmax_ws, hipStream_t stream) {
+  MMB_REQUIRE(table_bytes(table_type) != 0 && frame_bytes(frame_type) != 0);
+  return narrow_project(table_type, frame_type, ids, table, v, wtab32, text_cache, audio, visual, n, t, d, a_, vd,
+                        wpieces, c0, num_out, aux_out, mmb2_out, flag, colmax, colmax_ws, stream);
 }
 
 // the tools build's two-team variant (tools/diag/); the product library

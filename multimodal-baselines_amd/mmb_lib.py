@@ -30,8 +30,9 @@ MMB_FLAG_SYNC_TIMEOUT = 4
 # frame element types of mmb_mm2_stream_ft, mmb_mm2_stream_split_ft,
 # mmb_mm2_stream_project_ft and mmb_mm2_stream_project_narrow_ft
 MMB_FRAMES_F32, MMB_FRAMES_F16, MMB_FRAMES_BF16 = 0, 1, 2
-# word-table element types of mmb_sif_wavg_tt, mmb_mm2_stream_tt and
-# mmb_mm2_stream_project_tt
+# word-table element types of mmb_sif_wavg_tt, mmb_mm2_stream_tt,
+# mmb_mm2_stream_split_tt, mmb_mm2_stream_project_tt, mmb_mm2_text_cache_tt and
+# mmb_mm2_stream_project_narrow_tt
 MMB_TABLE_F32, MMB_TABLE_F16, MMB_TABLE_BF16 = 0, 1, 2
 
 _P = ctypes.c_void_p
@@ -84,6 +85,8 @@ SIGNATURES = {
                                   _I, _P, _P, _P, _P, _I, _P, _S, _P]),
     "mmb_mm2_stream_split_ft": (_I, [_P, _P, _L, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _P, _I,
                                      _P, _P, _P, _P, _I, _P, _S, _P]),
+    "mmb_mm2_stream_split_tt": (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _P, _I,
+                                     _P, _P, _P, _P, _I, _P, _S, _P]),
     "mmb_mm2_stream_project_supported": (_I, [_I, _I, _I, _I]),
     "mmb_mm2_stream_project": (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P,
                                     _P, _P, _P, _P, _P, _P, _P]),
@@ -94,10 +97,13 @@ SIGNATURES = {
     "mmb_mm2_prepare": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     "mmb_mm2_text_cache_bytes": (_S, [_L, _I]),
     "mmb_mm2_text_cache": (_I, [_P, _L, _I, _P, _P, _I, _P, _P]),
+    "mmb_mm2_text_cache_tt": (_I, [_P, _I, _L, _I, _P, _P, _I, _P, _P]),
     "mmb_mm2_stream_project_narrow_supported": (_I, [_I, _I, _I, _I, _L]),
     "mmb_mm2_stream_project_narrow": (_I, [_P, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P,
                                            _P, _P, _P, _P, _P, _P, _P, _P]),
     "mmb_mm2_stream_project_narrow_ft": (_I, [_P, _P, _L, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I,
+                                              _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mmb_mm2_stream_project_narrow_tt": (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I,
                                               _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mmb_mm2_split_bytes": (_S, [_I, _I, _I]),
     "mmb_mm2_split_pieces_bytes": (_S, [_I, _I, _I]),

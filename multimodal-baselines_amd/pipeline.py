@@ -101,9 +101,11 @@ def seq2weight(seq32: torch.Tensor, sel: torch.Tensor | None, wtab64: torch.Tens
 
 # Storage types of the word table: the name step_plan and FusedStep use ->
 # (torch dtype, the table_type of mmb_sif_wavg_tt / mmb_mm2_stream_tt).  The
-# 16-bit kinds are read by the SIF gather, the plain stream kernels and the
-# fused stream + projection kernel (weighted_sum, sif_embeddings, mm2_stream,
-# mm2_stream_project_tt); nothing here converts a table.
+# 16-bit kinds are read by the SIF gather, the plain stream kernels, the split
+# stream, the fused stream + projection kernel and the builder of the narrow
+# fused kernel's text cache (weighted_sum, sif_embeddings, mm2_stream,
+# mm2_stream_split_tt, mm2_stream_project_tt, mm2_stream_project_narrow_tt with
+# MMB2Projection.enable_text_cache(table16=True)); nothing here converts a table.
 TABLE_KINDS = {"f32": (torch.float32, L.MMB_TABLE_F32),
                "f16": (torch.float16, L.MMB_TABLE_F16),
                "bf16": (torch.bfloat16, L.MMB_TABLE_BF16)}
@@ -457,7 +459,7 @@ class MMB2Projection:
             self._build_text_cache()
         self._seen = self._versions()
 
-    def enable_text_cache(self, table: torch.Tensor, wtab32: torch.Tensor):
+    def enable_text_cache(self, table: torch.Tensor, wtab32: torch.Tensor, *, table16: bool = False):
         """Also keep the text cache of the narrow fused step
         (mmb_mm2_text_cache: P = E Wm_t1 + E^2 Wm_t2 per word, f64 rounded
         once, and the hot-word ranks), rebuilt with every re-merge and when
@@ -466,8 +468,12 @@ class MMB2Projection:
         tensors (identity here, storage address + version counter in
         refresh_if_changed); writes into them that bump neither (raw-pointer
         writes by other libmmb kernels, `t.data.copy_`) need invalidate().
-        The cache is built from a float32 table only."""
-        _f32_table(table, "MMB2Projection.enable_text_cache")
+        The cache is built from a float32 table only -- unless `table16=True`
+        opts in to a float16 / bfloat16 table (mmb_mm2_text_cache_tt: the
+        cache, float32 either way, is byte for byte that of the table upcast
+        to float32; the mirror of mmb_mm2_stream_project_narrow_tt asks for it)."""
+        if not table16 or table_kind(table, "MMB2Projection.enable_text_cache") == "f32":
+            _f32_table(table, "MMB2Projection.enable_text_cache")
         src = getattr(self, "text_src", None)
         if (getattr(self, "text_cache", None) is None or src[0] is not table
                 or src[1] is not wtab32):
@@ -483,6 +489,12 @@ class MMB2Projection:
 
     def _build_text_cache(self):
         table, wtab32 = self.text_src
+        tkind = table_kind(table, "MMB2Projection.enable_text_cache")
+        if tkind != "f32":  # (enable_text_cache(table16=True) let it in)
+            L.call("mmb_mm2_text_cache_tt", L.ptr(table, L.TABLE), TABLE_KINDS[tkind][1], table.shape[0], self.d,
+                   L.ptr(wtab32, L.F32), L.ptr(self.wm, L.F32), self.ldw, L.ptr(self.text_cache, L.BYTES),
+                   L.stream_ptr())
+            return
         L.call("mmb_mm2_text_cache", L.ptr(table, L.F32), table.shape[0], self.d, L.ptr(wtab32, L.F32),
                L.ptr(self.wm, L.F32), self.ldw, L.ptr(self.text_cache, L.BYTES), L.stream_ptr())
 
@@ -672,6 +684,35 @@ def mm2_stream_split_ft(n, t, d, a, vd, audio, visual, ids32, table, wtab32=None
     return num, s, aux
 
 
+def mm2_stream_split_tt(n, t, d, a, vd, audio, visual, ids32, table, wtab32=None, w_dense=None,
+                        flag=None, out=None, s_half: bool = True, colmax=None, colmax_ws=None,
+                        split=None, parts: int = 0):
+    """mm2_stream_split_ft on a word table of any TABLE_KINDS dtype as well
+    (mmb_mm2_stream_split_tt; gathered text only, all nine pairs of table and
+    frame dtypes): `table` may be float16 or bfloat16 -- the text in 4-value
+    units from an 8-byte aligned base at d % 4 == 0, in scalar loads
+    otherwise, never from an odd address -- and the outputs are bit for bit
+    those of mm2_stream_split_ft with the same `parts` on the same table
+    upcast to float32 (with one range: those of mm2_stream on the 16-bit
+    table).  `split` is a split_ws scratch (None: allocated here for
+    `parts`).  Returns (x, s, aux)."""
+    who = "mm2_stream_split_tt"
+    kind = frame_kind(audio, visual, who)
+    if ids32 is None or table is None:
+        raise L.MMBError(f"{who}: gathered text (ids32 + table) only; dense text is float32 and reads no table")
+    tkind = table_kind(table, who)
+    num, s, aux = _stream_outputs(who, kind, n, d, a, vd, audio, visual, table, out, s_half, colmax_ws,
+                                  text_kind=tkind)
+    if split is None:
+        split = split_ws(n, t, d, a, vd, audio.device, parts)
+    L.call("mmb_mm2_stream_split_tt", L.ptr(ids32, L.I32), L.ptr(table, L.TABLE), TABLE_KINDS[tkind][1],
+           table.shape[0], L.ptr(wtab32, L.F32), L.ptr(w_dense, L.F32), L.ptr(audio, L.FRAMES),
+           L.ptr(visual, L.FRAMES), FRAME_KINDS[kind][1], n, t, d, a, vd, L.ptr(num, L.F32), L.ptr(s, L.S_BUF),
+           int(s_half), L.ptr(aux, L.F32), L.ptr(flag, L.I32), L.ptr(colmax, L.I32), L.ptr(colmax_ws, L.BYTES),
+           int(parts), L.ptr(split, L.BYTES), split.numel() * split.element_size(), L.stream_ptr())
+    return num, s, aux
+
+
 # Narrowest frame row (floats) for which the fused stream + projection step is
 # the default: its 4 streaming waves per CU load every modality row as 16-B
 # columns on 64 lanes, so a frame row under 256 floats leaves lanes idle and
@@ -747,6 +788,32 @@ def mm2_stream_project_narrow_ft(n, t, d, a, vd, audio, visual, proj: "MMB2Proje
     bit those of the same frames upcast to float32.  Returns (x, aux, mmb2)."""
     return _stream_project("mm2_stream_project_narrow_ft", True, True, (), n, t, d, a, vd, audio, visual,
                            proj, ids32, table, wtab32, flag, out, colmax, colmax_ws)
+
+
+def mm2_stream_project_narrow_tt(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", ids32,
+                                 table, wtab32, flag=None, out=None, colmax=None, colmax_ws=None):
+    """mm2_stream_project_narrow_ft on a word table of any TABLE_KINDS dtype as
+    well (mmb_mm2_stream_project_narrow_tt; all nine pairs of table and frame
+    dtypes): `table` may be float16 or bfloat16.  The kernel takes its text
+    from the projection's text cache, built here from the 16-bit table
+    (enable_text_cache(table16=True): byte for byte the cache of the upcast
+    table), and never reads the table itself -- the outputs are bit for bit
+    those of mm2_stream_project_narrow_ft on the same table upcast to
+    float32.  Returns (x, aux, mmb2)."""
+    who = "mm2_stream_project_narrow_tt"
+    kind = frame_kind(audio, visual, who)
+    if ids32 is None or table is None:
+        raise L.MMBError(f"{who}: gathered text (ids32 + table) only; dense text is float32 and reads no table")
+    tkind = table_kind(table, who)
+    _check_colmax_ws(colmax_ws, d)  # (before the cache is built: a rejected call launches nothing)
+    proj.enable_text_cache(table, wtab32, table16=True)
+    num, aux, mmb2 = _fused_outputs(n, d, audio.device, out, colmax_ws)
+    L.call("mmb_mm2_stream_project_narrow_tt", L.ptr(ids32, L.I32), L.ptr(table, L.TABLE), TABLE_KINDS[tkind][1],
+           table.shape[0], L.ptr(wtab32, L.F32), L.ptr(proj.text_cache, L.BYTES), L.ptr(audio, L.FRAMES),
+           L.ptr(visual, L.FRAMES), FRAME_KINDS[kind][1], n, t, d, a, vd, L.ptr(proj.wpieces, L.BYTES),
+           L.ptr(proj.c0, L.F32), L.ptr(num, L.F32), L.ptr(aux, L.F32), L.ptr(mmb2, L.F32),
+           L.ptr(flag, L.I32), L.ptr(colmax, L.I32), L.ptr(colmax_ws, L.BYTES), L.stream_ptr())
+    return num, aux, mmb2
 
 
 def mm2_stream_project(n, t, d, a, vd, audio, visual, proj: "MMB2Projection", ids32=None,
@@ -959,7 +1026,8 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
               fork_projection: bool | None = None, split_stream: bool | None = None,
               split_projection: bool = True, frames: str = "f32",
               fused_frames16: bool = False, narrow_frames16: bool = False,
-              split_frames16: bool = False, fused_table16: bool = False,
+              split_frames16: bool = False, narrow_table16: bool = False,
+              split_table16: bool = False, fused_table16: bool = False,
               table: str = "f32") -> StepPlan:
     """The plan of a step over `n` of a split's `n_total` utterances on a chip
     of `cus` CUs; the remaining arguments are FusedStep's overrides (None: by
@@ -988,17 +1056,31 @@ def step_plan(n: int, n_total: int, t: int, d: int, a: int, vd: int, V: int, npc
     opts in to the wide-frame fused kernel on it (mmb_mm2_stream_project_tt):
     `stream_project` then keeps the caller's value and the front is "fused"
     exactly where the f32-table plan of the same shape and frames chooses it
-    (on 16-bit frames that still needs `fused_frames16`); `narrow_fused` and
-    `split_stream` stay off.  With "f32" the keyword changes nothing and every
-    plan is as described above.  The table kind is not a field of the plan."""
+    (on 16-bit frames that still needs `fused_frames16`).  `narrow_table16`
+    is its sibling for the narrow fused kernel
+    (mmb_mm2_stream_project_narrow_tt, its text cache built from the 16-bit
+    table): `narrow_fused` then keeps the caller's value and the front is
+    "narrow_fused" exactly where the f32-table plan of the same shape and
+    frames chooses it (on 16-bit frames that still needs `narrow_frames16`).
+    `split_table16` is the third sibling, for the split stream
+    (mmb_mm2_stream_split_tt): `split_stream` then keeps the caller's value
+    and `split` is set exactly where the f32-table plan of the same shape and
+    frames sets it (on 16-bit frames that still needs `split_frames16`).
+    Without its opt-in a front stays off.  With "f32" the three keywords
+    change nothing and every plan is as described above.  The table kind is
+    not a field of the plan."""
     check_npc(npc)
     if frames not in FRAME_KINDS:
         raise ValueError(f"frames must be one of {', '.join(FRAME_KINDS)}, not {frames!r}")
     if table not in TABLE_KINDS:
         raise ValueError(f"table must be one of {', '.join(TABLE_KINDS)}, not {table!r}")
     if table != "f32":
-        narrow_fused = split_stream = False
-        narrow_frames16 = split_frames16 = False
+        if not narrow_table16:
+            narrow_fused = False
+            narrow_frames16 = False
+        if not split_table16:
+            split_stream = False
+            split_frames16 = False
         if not fused_table16:
             stream_project = False
             fused_frames16 = False
@@ -1065,6 +1147,8 @@ _FRONTS = {"fused": ("mm2_stream_project", mm2_stream_project),
            "narrow_fused": ("mm2_stream_project_narrow", mm2_stream_project_narrow)}
 # their mirrors on 16-bit frames (the same phase names)
 _FRONTS_FT = {"fused": mm2_stream_project_ft, "narrow_fused": mm2_stream_project_narrow_ft}
+# and on a 16-bit word table, frames of any kind (fused_table16 / narrow_table16)
+_FRONTS_TT = {"fused": mm2_stream_project_tt, "narrow_fused": mm2_stream_project_narrow_tt}
 
 
 class FusedStep:
@@ -1125,8 +1209,12 @@ class FusedStep:
     `fused_table16=True` opts in to the fused stream + projection kernel on it
     where the f32-table plan of the shape and frames would choose it
     (mm2_stream_project_tt: no s buffer, the same rows bit for bit; on 16-bit
-    frames together with `fused_frames16`).  The narrow fused kernel and the
-    split stream read a float32 table only.
+    frames together with `fused_frames16`), `narrow_table16=True` to the
+    narrow fused kernel in the same way (mm2_stream_project_narrow_tt: the
+    text cache is built from the 16-bit table, byte for byte that of the
+    upcast table; on 16-bit frames together with `narrow_frames16`), and
+    `split_table16=True` to the split stream of the two-kernel step
+    (mm2_stream_split_tt; on 16-bit frames together with `split_frames16`).
 
     Which of these a step takes is decided once, by step_plan() (`self.plan`);
     _run is one sequence over it: front kernel, chunk pipeline, projection
@@ -1142,6 +1230,7 @@ class FusedStep:
                  fork_projection: bool | None = None, split_stream: bool | None = None,
                  split_projection: bool = True, fused_frames16: bool = False,
                  narrow_frames16: bool = False, split_frames16: bool = False,
+                 narrow_table16: bool = False, split_table16: bool = False,
                  fused_table16: bool = False):
         self.inp = inputs
         self.check_each_run = check_each_run
@@ -1160,7 +1249,8 @@ class FusedStep:
         # dtype its kernels would read as another
         self.frames = frame_kind(inputs["audio"], inputs["visual"], "FusedStep")
         # the word table's, likewise: a 16-bit table takes the two-kernel step
-        # (or, with fused_table16, the fused front's mm2_stream_project_tt)
+        # (or, with fused_table16 / narrow_table16 / split_table16, the `_tt`
+        # mirror of the front the f32-table plan chooses)
         self.table_kind = table_kind(self.table, "FusedStep")
         # and the ids' and the weight table's: int64 ids would be read as
         # pairs of int32, float64 weights as pairs of float32
@@ -1174,6 +1264,7 @@ class FusedStep:
                                   split_stream=split_stream, split_projection=split_projection,
                                   frames=self.frames, fused_frames16=fused_frames16,
                                   narrow_frames16=narrow_frames16, split_frames16=split_frames16,
+                                  narrow_table16=narrow_table16, split_table16=split_table16,
                                   fused_table16=fused_table16, table=self.table_kind)
         self.proj = MMB2Projection(networks, self.d, self.a, self.vd, self.t, dev)
         kp = self.proj.kp
@@ -1182,7 +1273,8 @@ class FusedStep:
         if p.front == "fused":
             self.proj.enable_pieces()
         if p.front == "narrow_fused":
-            self.proj.enable_text_cache(self.table, inputs["wtab"])
+            # (a 16-bit table gets here with narrow_table16 only)
+            self.proj.enable_text_cache(self.table, inputs["wtab"], table16=self.table_kind != "f32")
         self.G = torch.empty((self.d, self.d), dtype=torch.float64, device=dev)
         self.pc_buf = torch.empty((npc, self.d), dtype=torch.float64, device=dev)
         self.solve_ws = (torch.zeros(L.query("mmb_pc_solve_mc_ws_bytes", self.d), dtype=torch.uint8,
@@ -1292,8 +1384,13 @@ class FusedStep:
     def _stream_chunk(self, c: int):
         r0, r1 = self.bounds[c]
         inp = self.inp
-        # the split stream on 16-bit frames (split_frames16) has its own mirror
-        stream = mm2_stream_split_ft if self.split is not None and self.frames != "f32" else mm2_stream
+        # the split stream on a 16-bit table (split_table16) or on 16-bit
+        # frames (split_frames16) has its own mirror
+        stream = mm2_stream
+        if self.split is not None and self.table_kind != "f32":
+            stream = mm2_stream_split_tt
+        elif self.split is not None and self.frames != "f32":
+            stream = mm2_stream_split_ft
         stream(r1 - r0, self.t, self.d, self.a, self.vd, inp["audio"][r0:r1],
                inp["visual"][r0:r1], ids32=self.ids[r0:r1], table=self.table,
                wtab32=inp["wtab"], flag=self.flag, s_half=self.s_half,
@@ -1401,8 +1498,8 @@ class FusedStep:
             phase, front = _FRONTS[p.front]
             if p.frames != "f32":  # the fused kernels on 16-bit frames (fused_frames16 / narrow_frames16)
                 front = _FRONTS_FT[p.front]
-            if self.table_kind != "f32":  # the fused kernel on a 16-bit table (fused_table16), any frames
-                front = mm2_stream_project_tt
+            if self.table_kind != "f32":  # on a 16-bit table (fused_table16 / narrow_table16), any frames
+                front = _FRONTS_TT[p.front]
             with mark(phase):
                 front(self.n, self.t, self.d, self.a, self.vd, self.inp["audio"],
                       self.inp["visual"], self.proj, ids32=self.ids, table=self.table,

@@ -25,6 +25,19 @@ Prints median (min .. max) per variant, the frame-byte rate as a fraction of
 lies below the other's by more than the larger min .. max spread of the two.
 
     python tools/split_ab.py --frames16 [--reps 20] [--rounds 5]
+
+--table16: the split stream on a 16-bit word table (mmb_mm2_stream_split_tt),
+product library.  Per split and table type, on f32 frames, graph-timed and
+alternated in the same way:
+
+    f32_split        the f32 split stream (automatic parts)
+    <kind>_one       the one-workgroup launch on the 16-bit table
+                     (mmb_mm2_stream_tt): what such a table gets without the split
+    <kind>_split     the split stream on the 16-bit table (automatic parts)
+
+Prints median (min .. max) per variant and the verdicts by the same rule.
+
+    python tools/split_ab.py --table16 [--reps 20] [--rounds 5]
 """
 import argparse
 import json
@@ -54,6 +67,7 @@ ap.add_argument("--lib", default=None)
 ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--parts", default="0,2,3,4,6,8,12,16")
 ap.add_argument("--frames16", action="store_true")
+ap.add_argument("--table16", action="store_true")
 ap.add_argument("--rounds", type=int, default=5)
 args = ap.parse_args()
 dev = L.require_gpu()
@@ -161,8 +175,60 @@ def frames16_ab():
             print(f"  {kind}: u16 faster than u8 {faster(c16, c8)}, u8 faster than u16 {faster(c8, c16)}", flush=True)
 
 
+def table16_ab():
+    kinds = {"bf16": torch.bfloat16, "f16": torch.float16}
+    for si, inp in enumerate(splits):
+        keep = []  # (every tensor a captured graph reads stays referenced: see frames16_ab)
+        n, t = inp["ids"].shape
+        ws = P.split_ws(n, t, 300, 300, 300, dev)
+        mk = lambda: (torch.empty((n, 300), device=dev),  # noqa: E731
+                      P.s_buffer(n, P.mm2_dims(300, 300, 300)[0], True, dev), torch.empty((3, n), device=dev))
+        au, vi, ids, wtab = inp["audio"], inp["visual"], inp["ids"], inp["wtab"]
+        graphs, outs = {}, {}
+        outs["f32_split"] = mk()
+        graphs["f32_split"] = graph_of(lambda: P.mm2_stream(n, t, 300, 300, 300, au, vi, ids32=ids, table=inp["table"],
+                                                            wtab32=wtab, out=outs["f32_split"], split=ws))
+        for kind, dt in kinds.items():
+            E16 = inp["table"].to(dt)
+            keep.append(E16)
+            outs[f"{kind}_one"] = mk()
+            graphs[f"{kind}_one"] = graph_of(lambda: P.mm2_stream(n, t, 300, 300, 300, au, vi, ids32=ids, table=E16,
+                                                                  wtab32=wtab, out=outs[f"{kind}_one"]))
+            outs[f"{kind}_split"] = mk()
+            graphs[f"{kind}_split"] = graph_of(lambda: P.mm2_stream_split_tt(n, t, 300, 300, 300, au, vi, ids, E16,
+                                                                             wtab32=wtab, out=outs[f"{kind}_split"],
+                                                                             split=ws))
+            # the 16-bit split stream is the f32 one on the upcast table
+            twin = P.mm2_stream(n, t, 300, 300, 300, au, vi, ids32=ids, table=E16.float(), wtab32=wtab, split=ws)
+            torch.cuda.synchronize()
+            for x16, x32 in zip(outs[f"{kind}_split"], twin):
+                assert torch.equal(x16, x32), (kind, "twin")
+        res = {k: [] for k in graphs}
+        for _ in range(args.rounds):
+            for _ in range(args.reps):
+                for k, g in graphs.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    g.replay()
+                    b.record()
+                    b.synchronize()
+                    res[k].append(a.elapsed_time(b) / 10 * 1e3)
+        print(f"split{si}: {n} x {t}, automatic parts {P.split_parts(n, t)}; f32 frames; us per call, "
+              f"median (min .. max)", flush=True)
+        for k, v in res.items():
+            print(f"  {k:16s} {statistics.median(v):7.1f} ({min(v):.1f} .. {max(v):.1f})")
+        for kind in kinds:
+            c = res[f"{kind}_split"]
+            print(f"  {kind} split: faster than one-workgroup {faster(c, res[f'{kind}_one'])}, than the f32 split "
+                  f"{faster(c, res['f32_split'])}; the f32 split faster than it {faster(res['f32_split'], c)}",
+                  flush=True)
+
+
 if args.frames16:
     frames16_ab()
+    sys.exit(0)
+if args.table16:
+    table16_ab()
     sys.exit(0)
 variants = ["one"] + [f"p{p}" for p in args.parts.split(",")]
 res = {}
